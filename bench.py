@@ -27,7 +27,16 @@ Launch: under torchrun (WORLD_SIZE set; --gpus must equal it), or plain
 `python bench.py --gpus N`, which starts the N rank processes itself (launch_ranks).
 
 
-Prints ONE JSON line (rank 0) with
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs /
+--dump / --ppm if asked and prints ONE JSON line (rank 0): metric, value, unit,
+higher_is_better, dtype, ms_per_step (the wall milliseconds one timed step took), the
+workload's config.  `--dump-outputs DIR` saves what the last timed step left for its
+caller as DIR/<name>.npy (float32): `framebuffer`, the (ny, nx, 3) linear image — on
+several ranks the one rank 0 unpacked from the gather — or, with --share-of,
+`share_packed`, that share's packed pixels.  Scene, camera and sample streams are
+procedural with a fixed seed, so two runs with the same arguments render the same job.
+
+With `--full` the line also carries (each takes GPU or CPU runs of its own)
   roofline: the megakernel is bound by VALU instruction issue.
     achieved = the wave-level VALU instructions of one launch (SQ_INSTS_VALU per
     sample from the committed rocprofv3 pass, profiles/r<NN>/traffic.json, for this
@@ -45,6 +54,7 @@ Prints ONE JSON line (rank 0) with
   cpu_baseline: the reference binary (oracle/_ref/ref_render, compiled from the
     reference's own sources) on this job's CPU cores, bounded sample; the flat list
     as shipped (main.cpp:291) and with a corrected BVH (bvh.h:29-54, slab fixed).
+  end_to_end: one more render timed from scene creation to the image in host memory.
 """
 import argparse
 import glob
@@ -345,7 +355,12 @@ def main():
                     help="default: c4 on one GPU, c5 (final() 1000^2 x 1000 spp, strong scaling) on several")
     ap.add_argument("--spp", type=int, default=0, help="override the config's spp")
     ap.add_argument("--chunk", type=int, default=0, help="samples per work item; 0 = the C ABI's default (1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the roofline (a counting render + the committed PMC profiles), the "
+                         "end-to-end render and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 saves what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--ppm", default="")
     ap.add_argument("--dump", default="", help="rank 0 saves the last step's float image (.npy) here")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -357,6 +372,8 @@ def main():
                     help="the C ABI's rt_dist_gather (ncclGather on its own RCCL comm; auto with nccl), or "
                          "torch.distributed.gather (auto with gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus or 1) > 1:
@@ -460,6 +477,65 @@ def main():
     value = samples_per_step * args.steps / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
 
+    def close():
+        if comm is not None:
+            comm.close()
+        scene.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    # what the last timed step left for its caller, before anything else renders into `out`
+    if rank == 0 and (args.ppm or args.dump or args.dump_outputs):
+        if share:   # that share's pixels, packed tile after tile
+            img = None
+            outputs = {"share_packed": out[: all_counts[0]].cpu().numpy().reshape(-1, 3)}
+        elif world == 1:
+            img = out[: nx * ny * 3].cpu().numpy().reshape(ny, nx, 3)
+        else:   # the last timed step's gathered shares, unpacked on the root
+            img = np.zeros((ny, nx, 3), np.float32)
+            for r in range(world):
+                src = recv[r * n_max:(r + 1) * n_max] if native else gather_list[r]
+                rtnw.unpack_tiles(src[: all_counts[r]].cpu().numpy(), all_tiles[r], img)
+        if img is not None:
+            outputs = {"framebuffer": img}
+            if args.ppm:
+                with open(args.ppm, "wb") as f:
+                    f.write(rtnw.ppm_text(rtnw.quantize(img)))
+            if args.dump:
+                np.save(args.dump, img)
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+    res = {
+        "metric": METRIC if cfg == "c4" else
+        f"Msamples/s (pixels×spp/s) + achieved HBM GB/s, {scene_name}() {w1}×{h1}×{spp}spp",
+        "value": value,
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": f"synthetic: procedural {scene_name}() scene built by the host API (main.cpp builders), "
+                f"counter-RNG samples, seed 2024",
+        "config": {"workload": workload, "image": [nx, ny], "spp": spp, "pixels_per_gpu": nx * ny // world,
+                   "rank_layout": layout_name(world) if world > 1 else None,
+                   "chunk": int(st["chunk"]),
+                   "gather": (("rt_dist_gather (ncclGather)" if native else
+                               f"torch.distributed.gather ({args.dist_backend})") if world > 1 else None),
+                   "parallelism": f"pixels x{world}" + (" + one gather" if world > 1 else "")},
+    }
+    if not args.full:   # the plain run: the headline figure and nothing that takes a run of its own
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        close()
+        return
+
     # roofline of this rank's megakernel launches (HIP events on the render stream)
     rank_samples = all_counts[rank] // 3 * spp
     avg_kernel_s = float(np.mean(kms)) / 1e3
@@ -552,55 +628,14 @@ def main():
             roof["traffic"] = tr
             roof["hbm_frac"] = tr / avg_kernel_s / (HBM_PEAK_GBS * 1e9)
 
-    if rank == 0 and (args.ppm or args.dump) and not share:
-        if world == 1:
-            img = out[: nx * ny * 3].cpu().numpy().reshape(ny, nx, 3)
-        else:   # the last timed step's gathered shares, unpacked on the root
-            img = np.zeros((ny, nx, 3), np.float32)
-            for r in range(world):
-                src = recv[r * n_max:(r + 1) * n_max] if native else gather_list[r]
-                rtnw.unpack_tiles(src[: all_counts[r]].cpu().numpy(), all_tiles[r], img)
-        if args.ppm:
-            with open(args.ppm, "wb") as f:
-                f.write(rtnw.ppm_text(rtnw.quantize(img)))
-        if args.dump:
-            np.save(args.dump, img)
-
     if rank == 0:
-        res = {
-            "metric": METRIC if cfg == "c4" else
-            f"Msamples/s (pixels×spp/s) + achieved HBM GB/s, {scene_name}() {w1}×{h1}×{spp}spp",
-            "value": value,
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": f"synthetic: procedural {scene_name}() scene built by the host API (main.cpp builders), "
-                    f"counter-RNG samples, seed 2024",
-            "config": {"workload": workload, "image": [nx, ny], "spp": spp, "pixels_per_gpu": nx * ny // world,
-                       "rank_layout": layout_name(world) if world > 1 else None,
-                       "chunk": int(cst["chunk"]),
-                       "gather": (("rt_dist_gather (ncclGather)" if native else
-                                   f"torch.distributed.gather ({args.dist_backend})") if world > 1 else None),
-                       "parallelism": f"pixels x{world}" + (" + one gather" if world > 1 else "")},
-            "roofline": roof,
-            "cpu_baseline": None,
-        }
+        res.update(roofline=roof, cpu_baseline=None)
         if world == 1 and not share:
             res["end_to_end"] = end_to_end(scene_name, cam, params, nx, ny, dev)
         if world == 1 and not share and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(scene_name, w1, h1)
         print(json.dumps(res), flush=True)
-    if comm is not None:
-        comm.close()
-    scene.close()
-    if world > 1:
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

@@ -1,7 +1,9 @@
 """bench.py as the driver runs it for N GPUs: `python bench.py --gpus N` with no
 launcher around it starts the N rank processes itself (bench.launch_ranks), a
 `--gpus` that disagrees with a launcher's WORLD_SIZE is refused, a rank that dies
-takes the job down instead of leaving its peers in the rendezvous, and (GPU) the
+takes the job down instead of leaving its peers in the rendezvous, (GPU) a plain run
+reports the headline figure alone and `--dump-outputs` leaves the last step's image
+while `--full` adds the roofline and the end-to-end render, and (GPU) the
 2- and 8-rank jobs render config 5's workload whose gathered image is bitwise the
 1-GPU image (the RNG is keyed by pixel and sample)."""
 import json
@@ -50,6 +52,54 @@ def test_rccl_refuses_more_ranks_than_gpus():
     assert "one GPU per rank" in p.stderr
 
 
+def _bench_line(*argv):
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", *argv], env=_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+HEADLINE = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"}
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_image(tmp_path):
+    """A plain run reports the headline figure only (nothing that takes a run of its own),
+    --steps is the number of timed steps, and --dump-outputs leaves the last timed step's
+    image: the float32 framebuffer a 1-GPU render of the same job gives, bit for bit."""
+    out = tmp_path / "outputs"
+    line = _bench_line("--spp", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
+    assert HEADLINE <= set(line)
+    assert not {"roofline", "cpu_baseline", "end_to_end"} & set(line)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["config"]["spp"] == 2
+    assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] == pytest.approx(500 * 500 * 2 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-9)
+    assert sorted(os.listdir(out)) == ["framebuffer.npy"]
+    img = np.load(out / "framebuffer.npy")
+    assert img.dtype == np.float32 and img.shape == (500, 500, 3)
+
+    import rtnw
+    sc = rtnw.Scene.builtin("final", device=0)
+    cam = rtnw.Camera.preset("cornell", 500, 500)
+    one = sc.render_tile(cam, rtnw.RenderParams(500, 500, 2, max_depth=50, seed=2024), 0, 0, 500, 500)
+    sc.close()
+    assert np.array_equal(img.view(np.uint32), one.view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_roofline_and_the_end_to_end_render(tmp_path):
+    """--full keeps what a plain run no longer does: the counting render's roofline figures
+    and the end-to-end render (the CPU baseline too, left out here by --no-cpu-baseline);
+    the counting render does not reach the dumped image."""
+    out = tmp_path / "outputs"
+    line = _bench_line("--spp", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
+                       "--dump-outputs", str(out))
+    assert HEADLINE <= set(line)
+    assert line["roofline"]["bound"] == "valu_issue" and line["roofline"]["rays_per_sample"] > 1
+    assert line["end_to_end"]["value"] > 0 and line["cpu_baseline"] is None
+    assert np.load(out / "framebuffer.npy").shape == (500, 500, 3)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,spp", [(2, 8), (8, 2)])
 def test_self_launched_bench_gathers_the_one_gpu_image(tmp_path, n, spp):
@@ -61,7 +111,8 @@ def test_self_launched_bench_gathers_the_one_gpu_image(tmp_path, n, spp):
     for bit."""
     dump = str(tmp_path / f"c5_{n}ranks.npy")
     p = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--dist-backend", "gloo", "--spp", str(spp),
-                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dump", dump],
+                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--dump", dump,
+                        "--dump-outputs", str(tmp_path / "outputs")],
                        env=_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -74,6 +125,7 @@ def test_self_launched_bench_gathers_the_one_gpu_image(tmp_path, n, spp):
             "lattice": "8x8 block lattice %dx%d" % {2: (2, 1), 8: (4, 2)}[n]}[layout]
     assert line["config"]["rank_layout"] == want
     img = np.load(dump)
+    assert np.array_equal(np.load(tmp_path / "outputs" / "framebuffer.npy").view(np.uint32), img.view(np.uint32))
 
     import rtnw
     sc = rtnw.Scene.builtin("final", device=0)

@@ -29,7 +29,7 @@ for r in range(args.rounds):
             k, _, v = kv.partition("=")
             env[k] = v
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                              "--spp", str(args.spp), "--no-cpu-baseline"] + list(filter(None, bargs.split("+"))), env=env, capture_output=True, text=True,
+                              "--spp", str(args.spp), "--full", "--no-cpu-baseline"] + list(filter(None, bargs.split("+"))), env=env, capture_output=True, text=True,
                              timeout=int(os.environ.get("AB_RUN_TIMEOUT", "150")))
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

@@ -24,7 +24,7 @@ for step in "$@"; do
     tests)  run tests 1200 python -u -m pytest tests -m gpu -x -v -s --timeout 300 --timeout-method thread ;;
     testsk) run tests 1200 python -m pytest tests -m gpu -q -s ;;
     bench_small) run bench_small 600 python bench.py --spp 64 --steps 2 --warmup 1 --no-cpu-baseline ;;
-    bench)  run bench 900 python bench.py ;;
+    bench)  run bench 900 python bench.py --full ;;
     prof)   export TMPDIR=/tmp
             run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --config ${BENCH_CFG:-c4} --steps 5 --warmup 1 --no-cpu-baseline ;;
     counters) export TMPDIR=/tmp; run counters 120 rocprofv3 -L ;;

@@ -30,7 +30,7 @@ def kernel_ms(extra, lib):
     if lib:
         env["RTNW_LIB"] = os.path.abspath(lib)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     if not line:
         raise RuntimeError(out.stderr[-2000:])
