@@ -155,7 +155,20 @@ enum {
      * write the sums (to checkpoint or resume later); without it the output is the
      * mean, col * float(1.0 / ns) with ns = sample_offset + spp under SUM_IN, else spp. */
     RT_FLAG_SUM_IN = 4,
-    RT_FLAG_SUM_OUT = 8
+    RT_FLAG_SUM_OUT = 8,
+    /* Parity mode (DESIGN.md §7 "Right-fold mode"; speed is not its goal): each sample's
+     * radiance is computed as main.cpp:36's `emitted + attenuation*color(...)` from the
+     * deepest hit outwards (a right fold over the path's scatters), not by forward
+     * throughput.  The image then equals the reference binary's counter-RNG framebuffer
+     * bit for bit when chunk <= 1 or chunk >= spp (one add per sample, main.cpp:311).
+     * Media are still evaluated after the surface pass, not in list order (the DESIGN
+     * section records why no input tells the two apart).  Composes with sample_offset,
+     * SUM_IN / SUM_OUT, chunk, tiles and sample batches like a plain render; with
+     * RT_FLAG_COUNT or RT_FLAG_PROFILE it returns RT_ERR_INVALID, on a scene with a wide
+     * BVH (RTNW_BVH_WIDTH 4, 8, 8q) RT_ERR_UNSUPPORTED.  Every lane of the launch keeps a
+     * stack of max_depth attenuations (16 B each) in device memory; a max_depth whose
+     * stacks would pass the slab budget's default (16 GiB) returns RT_ERR_INVALID. */
+    RT_FLAG_RIGHT_FOLD = 16
 };
 
 typedef struct rt_render_params {
@@ -297,7 +310,9 @@ int rt_unpack_tiles(const float *packed, const int32_t *tiles, int64_t ntiles, i
 /* The whole rank job: this rank's pixels -> rt_render_tiles -> rt_dist_gather -> on the
  * root, the full nx x ny x 3 mean image in host memory (`image`; NULL on other ranks).
  * Mean images only: RT_FLAG_SUM_IN / RT_FLAG_SUM_OUT return RT_ERR_INVALID (on every
- * rank alike).  A rank whose render fails still joins the gather; one that cannot
+ * rank alike).  The other flags pass through to rt_render_tiles unchanged, so
+ * RT_FLAG_RIGHT_FOLD renders the right-fold image on every rank's share.
+ * A rank whose render fails still joins the gather; one that cannot
  * allocate its buffers aborts the communicator (ncclCommAbort, later calls on it fail)
  * and its launcher must stop the peers waiting in the gather. */
 int rt_dist_render(rt_dist *d, rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, float *image,

@@ -88,9 +88,19 @@ struct RtKernelArgs {
     // iterations after dry, live lanes summed over them, paths taken from the pools after dry,
     // the stage cycles after dry: claim, traverse, media, shade)
     unsigned long long *wave_log;
+    // right-fold variants (RT_FLAG_RIGHT_FOLD): every lane's stack of scatter attenuations,
+    // entry d of lane `slot` (blockIdx.x * blockDim.x + threadIdx.x) at fold[d * fold_stride + slot],
+    // d in [0, max_depth); fold_stride = the launch's lanes (grid x block)
+    float4 *fold;
+    uint32_t fold_stride;
 };
 
+// mode: 0 plain, 1 count, 2 profile, RT_LAUNCH_FOLD the plain right-fold variant (width 2 only)
+#define RT_LAUNCH_FOLD 3
+typedef hipError_t (*RtFoldLaunch)(const RtKernelArgs *a, int grid, hipStream_t stream);   // rt_kernel_fold.hip's launcher
 extern "C" hipError_t rt_launch_megakernel(const RtKernelArgs *a, int grid, int mode, hipStream_t stream);
+// 1 when the library holds the fold unit (a library linked from rt_kernel.o alone does not)
+extern "C" int rt_megakernel_has_fold(void);
 // Resolve of one sample batch (capi.cpp): adds the batch's partial sums to each
 // pixel's running sum in sample order.  mode: RT_RESOLVE_* bits.
 #define RT_RESOLVE_FIRST 1    // the first batch: start from 0 (or, with SUM_IN, from out)

@@ -101,6 +101,14 @@ enum : int { PH_IDLE = 0, PH_TRAV = 1, PH_READY = 2, PH_PARK = 3 };
 //      at launch; node steps read them with ds_read_b128), stacks of the scene's depth;
 //   2  flat scan of the primitive groups (rt_layout.h rt_dgroup), primitives in LDS,
 //      no BVH and no stack: scenes of at most RT_SCAN_MAX primitives.
+// kMode & 4 (kFold, RT_FLAG_RIGHT_FOLD): the right-fold variants of the plain width-2
+// kernels.  A sample's radiance is main.cpp:36's `emitted + attenuation*color(...)`
+// evaluated from the deepest hit outwards instead of throughput * emitted: each scatter
+// stores its attenuation in the lane's own stack in HBM (RtKernelArgs.fold, depth-major:
+// a wave's entries of one depth are contiguous), the path's end folds them back.  The
+// lane that writes an entry is the only one that reads it (no ball waves: paths stay in
+// their lane), so plain loads and stores in program order suffice.  The switch shares
+// the search mode's template argument so that the other variants keep their names.
 // Kernel arguments re-read each loop iteration: the persistent
 // loop reads ~40 uniform arguments; held in SGPRs across it they overflowed the 102
 // addressable SGPRs, which the compiler spilled into the lanes of a VGPR (v_writelane
@@ -115,26 +123,28 @@ __device__ __forceinline__ KArgs *opaque_kargs(KArgs *p) {
 }
 
 template <bool kCount, bool kProf, int kWidth, int kFeat, int kMode>
-__global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_SIMD) void rt_megakernel(RtKernelArgs A_param) {
+__global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_SIMD) void rt_megakernel(RtKernelArgs A_param) {
     (void)A_param;   // read through ka (the same bytes: the kernarg segment holds A_param at offset 0)
     KArgs *ka = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
 #define A (*(const RtKernelArgs *)ka)
     constexpr bool kInst = (kFeat & RT_FEAT_INST) != 0, kUV = (kFeat & RT_FEAT_UV) != 0,
                    kChecker = (kFeat & RT_FEAT_CHECKER) != 0, kPrescan = (kFeat & RT_FEAT_PRESCAN) != 0,
                    kMedia = (kFeat & RT_FEAT_MEDIA) != 0;
-    constexpr bool kLds = kMode == 1, kScan = kMode == 2;
+    constexpr int kSearch = kMode & 3;
+    constexpr bool kFold = (kMode & 4) != 0;
+    constexpr bool kLds = kSearch == 1, kScan = kSearch == 2;
     // the ball waves (stage 6) and the medium cell that ends their paths' closest-hit searches
     // (stage 3): the media variant without instance chains (final(); a cell needs a medium
     // bounded by one plain sphere, and the instance variants have no registers to spare) with
     // the BVH2 in LDS.  The cell is tested in ball waves only: in the others, whose lanes
     // mostly start outside the ball, its lockstep tests cost every lane (c4 +3.8 %)
-    constexpr bool kBall = kMedia && !kInst && kFeat != RT_FEAT_ALL && kLds && kWidth == 2;
+    constexpr bool kBall = kMedia && !kInst && kFeat != RT_FEAT_ALL && kLds && kWidth == 2 && !kFold;
     constexpr bool kCell = kBall;
     // the LDS node layout (rt_device.h RtSplit): dword planes in the media variants (final()),
     // float4 planes otherwise, as each measured fastest
-    constexpr int kSplit = rt_lds_split(kMode, kFeat, kWidth);
+    constexpr int kSplit = rt_lds_split(kSearch, kFeat, kWidth);
     constexpr int kBlock = kLds ? RT_LDS_BLOCK : RT_BLOCK;
-    __shared__ uint32_t lds_stack[kMode ? 1 : RT_BLOCK / 64][kMode ? 1 : (kWidth >= 8 ? RT_STACK_DEPTH_W8 : RT_STACK_DEPTH)][64];
+    __shared__ uint32_t lds_stack[kSearch ? 1 : RT_BLOCK / 64][kSearch ? 1 : (kWidth >= 8 ? RT_STACK_DEPTH_W8 : RT_STACK_DEPTH)][64];
     __shared__ CoopSlot lds_slots[kBlock / 64][64];
     __shared__ MediumRec lds_media[RT_LDS_MEDIA];
     __shared__ CamV4 lds_cam[6];
@@ -160,7 +170,7 @@ __global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_
     // (LDS variant: 16-bit entries, [wave][depth][lane], rt_device.h stk16_*)
     uint32_t *stk = kLds ? reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(lds_dyn) + lds_node_bytes<kSplit>() +
                                                         (wave * (uint32_t)A.stack_depth * 64u + lane) * 2u)
-                         : &lds_stack[kMode ? 0 : wave][0][lane];
+                         : &lds_stack[kSearch ? 0 : wave][0][lane];
     CoopSlot *slots = lds_slots[wave];
     uint64_t *pre_key = lds_pre_key[wave];
     float2 *pre_uv = lds_pre_uv[wave];
@@ -534,7 +544,7 @@ __global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_
             r.o = add(org, offset);
             r.d = dir;
             r.time = time;
-            beta = mk(1, 1, 1);
+            if (!kFold) beta = mk(1, 1, 1);
             depth = 0;
             if (kCount) cnt.samples++;
             if (seg) begin_segment();
@@ -550,10 +560,35 @@ __global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_
         phase = PH_IDLE;
     };
 
+    // (kFold) entry 0 of the lane's attenuation stack.  The address is made where it is
+    // used, from arguments re-read there (opaque_kargs) and a lane index the compiler
+    // cannot carry: hoisted out of the persistent loop it held two VGPRs and two SGPRs for
+    // the whole kernel, which spilled.
+    auto fold_base = [&]() -> float4 * {
+        KArgs *k = opaque_kargs(ka);
+        uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
+        asm volatile("" : "+v"(slot));
+        return k->fold + slot;
+    };
+    // (kFold) main.cpp:36 from the deepest hit outwards: L is the path end's own emitted
+    // value; every scatter above it returns emitted + attenuation * L, its emitted() the
+    // base class's vec3(0,0,0) (material.h:56) — the add stays: 0 + x is not x for x = -0
+    auto fold_path = [&](V3 L) -> V3 {
+        const float4 *f = fold_base();
+        for (int d = depth - 1; d >= 0; --d) {
+            const float4 att = f[(size_t)d * A.fold_stride];
+            L = add(mk(0, 0, 0), mul(mk(att.x, att.y, att.z), L));
+        }
+        return L;
+    };
+
     for (;;) {
         // (not in the flat-scan variant: its scan reads the group records right at the
-        // iteration's start, and the reload measured slower there, c2 37.63 -> 37.88 ms)
-        if (!kScan) ka = opaque_kargs(ka);
+        // iteration's start, and the reload measured slower there, c2 37.63 -> 37.88 ms; its
+        // fold variants do reload: holding the arguments in SGPRs across the loop beside
+        // fold_base's re-read ones spilled 4 SGPRs in two of them, 0 with the reload, and the
+        // mode's speed is no concern)
+        if (!kScan || kFold) ka = opaque_kargs(ka);
         // ---- 1. claims and camera samples for lanes without a path --------------
         // (the first iteration, and paths that ended after the shading stage's
         // cooperative rounds: a metal's absorbed reflection; the others start their
@@ -778,7 +813,11 @@ __global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_
                 if (sc) cnt.l_scatter++;
             }
         }
-        if (ends) end_path(mul(beta, shade_emitted(A, have, r, rd, st)));
+        if (ends) {
+            const V3 e = shade_emitted(A, have, r, rd, st);
+            if constexpr (kFold) end_path(fold_path(e));
+            else end_path(mul(beta, e));
+        }
         retire_and_claim(false);
         // (a lane left without work by a ball wave's claim, waiting for the pool, has no item)
         const bool starting = phase == PH_IDLE && !finished && (!kBall || item != 0xFFFFFFFFu);
@@ -795,10 +834,16 @@ __global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_
         if (ready && !ends) {
             const ShadeOut so = shade_finish(A, ready, have, r, rd, hr, st, pt, g);
             if (so.scattered) {
-                beta = mul(beta, so.att);
+                // (kFold) depth < max_depth here (ShadeState.live, main.cpp:34): the stack's bound
+                if constexpr (kFold)
+                    fold_base()[(size_t)depth * A.fold_stride] = make_float4(so.att.x, so.att.y, so.att.z, 0.f);
+                else
+                    beta = mul(beta, so.att);
                 r = so.ray;
                 ++depth;
                 seg = true;
+            } else if constexpr (kFold) {
+                end_path(fold_path(so.emitted));
             } else {
                 end_path(mul(beta, so.emitted));
             }
@@ -895,6 +940,12 @@ __global__ __launch_bounds__(kMode == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_
 
 #undef A
 
+// MEGAKERNEL_FOLD_UNIT (rt_kernel_fold.hip): the translation unit of the right-fold variants,
+// which the build compiles beside this one (the variant set's compile time is the library's
+// build time).  It takes the megakernel and its launchers from here, holds no other kernel
+// and defines rt_launch_megakernel_fold.  (Not an RT_* knob: every library build compiles
+// both of its values.)
+#ifndef MEGAKERNEL_FOLD_UNIT
 // Adds one sample batch's partial sums to each pixel's running sum, in sample
 // order (main.cpp:311 `col += temp`, one add per sample with one sample per work
 // item), so the image does not depend on how the samples were split into batches
@@ -950,6 +1001,7 @@ __global__ __launch_bounds__(256) void rt_math_probe_kernel(int fn, const float 
     }
     out[i] = r;
 }
+#endif  // MEGAKERNEL_FOLD_UNIT
 
 #ifdef RT_KNOB_CHECK
 // tests/test_device_knobs.py: a device-only build of final()'s variant (BVH2 in LDS, media)
@@ -961,15 +1013,17 @@ template __global__ void rt_megakernel<false, false, 2, RT_FEAT_INST, 2>(RtKerne
 }  // namespace
 
 #ifndef RT_KNOB_CHECK
+#ifndef MEGAKERNEL_FOLD_UNIT
 extern "C" hipError_t rt_launch_math_probe(int fn, const float *a, const float *b, float *out, int n, hipStream_t stream) {
     hipLaunchKernelGGL(rt_math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, a, b, out, n);
     return hipGetLastError();
 }
+#endif
 
 // --------------------------------------------------------------- launchers
-template <bool kCount, bool kProf, int kWidth, int kFeat, int kLds>
+template <bool kCount, bool kProf, int kWidth, int kFeat, int kLds, bool kFold = false>
 static hipError_t launch_one(const RtKernelArgs *a, int grid, hipStream_t stream) {
-    auto *k = rt_megakernel<kCount, kProf, kWidth, kFeat, kLds>;
+    auto *k = rt_megakernel<kCount, kProf, kWidth, kFeat, kLds | (kFold ? 4 : 0)>;
     size_t dyn = 0;
     if (kLds == 1) {
         // the variant's node layout (rt_megakernel's kSplit): dword planes need 56 KiB, float4 planes 64
@@ -1000,9 +1054,17 @@ static hipError_t launch_one(const RtKernelArgs *a, int grid, hipStream_t stream
 
 template <int kWidth, int kFeat, int kLds>
 static hipError_t launch_variant(const RtKernelArgs *a, int grid, int mode, hipStream_t stream) {
+#ifdef MEGAKERNEL_FOLD_UNIT
+    // the right-fold variants (rt_megakernel kFold): plain mode, width 2 (capi.cpp checks both)
+    if constexpr (kWidth == 2)
+        if (mode == RT_LAUNCH_FOLD) return launch_one<false, false, kWidth, kFeat, kLds, true>(a, grid, stream);
+    return hipErrorInvalidValue;
+#else
     if (mode == 1) return launch_one<true, false, kWidth, kFeat, kLds>(a, grid, stream);
     if (mode == 2) return launch_one<false, true, kWidth, kFeat, kLds>(a, grid, stream);
+    if (mode != 0) return hipErrorInvalidValue;
     return launch_one<false, false, kWidth, kFeat, kLds>(a, grid, stream);
+#endif
 }
 
 // The compiled variant that runs a scene's features (launch_features below).
@@ -1036,7 +1098,24 @@ static hipError_t launch_features(const RtKernelArgs *a, int grid, int mode, hip
 // no feature), instances (cornell_box), instances + media (cornell_smoke), checker +
 // pre-scan without media (the random scenes), each with the BVH2 in HBM or in LDS; the
 // wide BVHs (4, 8, compressed 8) run the all-feature variant from HBM.
+#ifdef MEGAKERNEL_FOLD_UNIT
+// ... and the right-fold variant of each width-2 one (plain mode only)
+extern "C" hipError_t rt_launch_megakernel_fold(const RtKernelArgs *a, int grid, hipStream_t stream) {
+    if (a->bvh_width != 2) return hipErrorInvalidValue;
+    if (a->scan) return launch_features<2>(a, grid, RT_LAUNCH_FOLD, stream);
+    return a->lds_nodes ? launch_features<1>(a, grid, RT_LAUNCH_FOLD, stream) : launch_features<0>(a, grid, RT_LAUNCH_FOLD, stream);
+}
+// the unit announces its launcher to rt_launch_megakernel when it is linked in
+extern "C" RtFoldLaunch rt_fold_launch;
+static const bool fold_unit_linked = (rt_fold_launch = rt_launch_megakernel_fold, true);
+#else
+// the fold unit's launcher, set by that unit's static initialiser: this object links and
+// runs every other variant without it (a fold launch is then an error, not another kernel)
+extern "C" RtFoldLaunch rt_fold_launch;
+RtFoldLaunch rt_fold_launch = nullptr;
+extern "C" int rt_megakernel_has_fold(void) { return rt_fold_launch != nullptr; }
 extern "C" hipError_t rt_launch_megakernel(const RtKernelArgs *a, int grid, int mode, hipStream_t stream) {
+    if (mode == RT_LAUNCH_FOLD) return rt_fold_launch ? rt_fold_launch(a, grid, stream) : hipErrorInvalidDeviceFunction;
     if (a->scan) return launch_features<2>(a, grid, mode, stream);
     if (a->bvh_width == 4) return launch_variant<4, RT_FEAT_ALL, 0>(a, grid, mode, stream);
     if (a->bvh_width == 8) return launch_variant<8, RT_FEAT_ALL, 0>(a, grid, mode, stream);
@@ -1109,4 +1188,5 @@ extern "C" int rt_megakernel_lds_static_bytes(void) {
     return (int)(4 * 64 + (RT_LDS_BLOCK / 64) * 64 * sizeof(CoopSlot) + RT_LDS_MEDIA * sizeof(MediumRec) + 6 * 16 + 16 +
                  (RT_LDS_BLOCK / 64) * RT_PRE * (8 + 8 + 8) + RT_LCG_JUMPS * 16 + 2 * 80 + 16 + 16 + 4) + 256;
 }
+#endif  // MEGAKERNEL_FOLD_UNIT
 #endif  // RT_KNOB_CHECK

@@ -178,6 +178,8 @@ struct rt_scene {
     size_t slab_bytes = 0;
     void *acc = nullptr;          // per-pixel running sums between sample batches
     size_t acc_bytes = 0;
+    void *fold = nullptr;         // RT_FLAG_RIGHT_FOLD: the lanes' attenuation stacks (rt_kernel.h RtKernelArgs.fold)
+    size_t fold_bytes = 0;
     void *counter = nullptr, *stats = nullptr;
     void *host_out = nullptr;
     size_t host_out_bytes = 0;
@@ -320,7 +322,7 @@ static int validate_desc(const rt_scene_desc *d) {
 void rt_scene_destroy(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    for (void *p : {s->arena, s->job_xy, s->job_out, s->slab, s->acc, s->counter, s->host_out})
+    for (void *p : {s->arena, s->job_xy, s->job_out, s->slab, s->acc, s->fold, s->counter, s->host_out})
         if (p) (void)hipFree(p);
     for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
@@ -817,6 +819,24 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
     if (p->nx <= 0 || p->ny <= 0 || p->spp <= 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "bad render parameters");
     if (s->has_moving && (cam->time0 < s->time0 || cam->time1 > s->time1))
         return fail(RT_ERR_INVALID, "camera shutter outside the scene's time span (moving-sphere bounds)");
+    // RT_FLAG_RIGHT_FOLD (rt_hip.h): plain renders of width-2 scenes only, and a stack of
+    // max_depth attenuations (16 B each) for every lane of the launch, within the slab
+    // budget's default (RTNW_SLAB_BUDGET shapes the sample batches, not this bound)
+    const bool fold = (p->flags & RT_FLAG_RIGHT_FOLD) != 0;
+    const uint64_t fold_lanes = (uint64_t)s->grid[0] * (s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK);
+    const uint64_t fold_bytes = fold ? fold_lanes * (uint64_t)std::max(1, p->max_depth) * sizeof(float4) : 0;
+    if (fold) {
+        if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE))
+            return fail(RT_ERR_INVALID, "RT_FLAG_RIGHT_FOLD cannot be combined with RT_FLAG_COUNT or RT_FLAG_PROFILE");
+        if (s->bvh_width != 2)
+            return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_RIGHT_FOLD needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
+        if (!rt_megakernel_has_fold())
+            return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_RIGHT_FOLD: this library was linked without the fold variants (rt_kernel_fold.o)");
+        if (fold_bytes > RT_SLAB_BUDGET)
+            return fail(RT_ERR_INVALID, "RT_FLAG_RIGHT_FOLD: max_depth " + std::to_string(p->max_depth) + " needs a " +
+                                            std::to_string(fold_bytes) + "-byte attenuation stack, over the " +
+                                            std::to_string(RT_SLAB_BUDGET) + "-byte budget");
+    }
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)stream_v;
     if (int rc = prepare_job(s, tiles, ntiles, p->nx, p->ny, cam)) return rc;
@@ -855,6 +875,13 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
         s->acc_bytes = 0;
         HIP_TRY(hipMalloc(&s->acc, acc_bytes));
         s->acc_bytes = acc_bytes;
+    }
+    if (fold_bytes > s->fold_bytes) {
+        if (s->fold) (void)hipFree(s->fold);
+        s->fold = nullptr;
+        s->fold_bytes = 0;
+        HIP_TRY(hipMalloc(&s->fold, fold_bytes));
+        s->fold_bytes = fold_bytes;
     }
     const bool count = (p->flags & RT_FLAG_COUNT) != 0;
     const bool prof = !count && (p->flags & RT_FLAG_PROFILE) != 0;
@@ -938,6 +965,8 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
         HIP_TRY(hipMemsetAsync(wave_log, 0, wave_log_n * sizeof(unsigned long long), stream));
     }
     a.wave_log = wave_log;
+    a.fold = fold ? (float4 *)s->fold : nullptr;
+    a.fold_stride = (uint32_t)fold_lanes;
 
     // vec3::operator/= (vec3.h:134-141): col *= float(1.0 / ns)
     const uint32_t ns_total = sum_in ? p->sample_offset + (uint32_t)p->spp : (uint32_t)p->spp;
@@ -978,7 +1007,7 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
         if (prof)
             HIP_TRY(hipMemsetAsync((unsigned long long *)s->stats + RT_STAT_TIME, 0, 7 * sizeof(unsigned long long), stream));
         HIP_TRY(hipEventRecord(s->ev[0], stream));
-        HIP_TRY(rt_launch_megakernel(&a, s->grid[mode], mode, stream));
+        HIP_TRY(rt_launch_megakernel(&a, s->grid[mode], fold ? RT_LAUNCH_FOLD : mode, stream));
         HIP_TRY(hipEventRecord(s->ev[1], stream));
         HIP_TRY(rt_launch_resolve((const float *)s->slab, s->npix, a.nchunks, k, (float4 *)s->acc, rmode,
                                   (const uint32_t *)s->job_out, out_dev, stream));

@@ -29,6 +29,7 @@ RT_FLAG_COUNT = 1
 RT_FLAG_PROFILE = 2
 RT_FLAG_SUM_IN = 4      # the output holds the sums of samples [0, sample_offset) on entry
 RT_FLAG_SUM_OUT = 8     # write per-pixel sums (checkpoints), not means
+RT_FLAG_RIGHT_FOLD = 16  # parity mode: main.cpp:36's right fold per sample (rt_hip.h)
 RT_CHECKPOINT_MAGIC = 0x4B435452
 
 
