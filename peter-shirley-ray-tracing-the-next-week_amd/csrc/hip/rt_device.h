@@ -503,6 +503,8 @@ struct Counters {
     // branches, the distinct materials each pass ran, and the lanes that scattered
     uint64_t w_shade = 0, w_kinds = 0, l_scatter = 0;
     uint64_t ball[RT_BALL_N] = {0, 0, 0, 0, 0, 0, 0, 0};   // the ball waves (rt_layout.h RT_BALL_*), wave-level
+    uint64_t w_local = 0;                                  // coop_reject_mixed's local candidate trips (part of w_rius)
+    uint64_t sampler[RT_SAMPLER_N] = {0, 0, 0, 0};         // rt_layout.h RT_SAMPLER_*, wave-level (lane 0)
     __device__ __forceinline__ void prim(int kind) {
         const int k = kind & 0xff;
         if (k == RT_PRIM_SPHERE) spheres++;
@@ -1099,13 +1101,42 @@ __device__ __forceinline__ V3 coop_reject(bool want, Rng &g, CoopSlot *slots, co
 // and each owner advances its stream by its own count: the points and draws are
 // exactly those of coop_reject<2> / coop_reject<3>.  Lets the megakernel run the
 // lens-disk candidates of new camera samples in the shading stage's rounds.
+//
+// Local first candidates (n_local 1..3, RtKernelArgs.coop_local): with m requesting
+// lanes a round hands each owner floor(64 / m) candidates, so a wave where most lanes
+// ask (the shading stage's ready batch, a ball wave's isotropic lanes) pays the whole
+// exchange for about one candidate per owner.  When at least n_min lanes request, each
+// of them first evaluates the next n_local candidates of its own stream, straight-line:
+// no LDS publish, jump-table read, bpermute or barrier.  These are the first iterations
+// of the owner's sequential loop, so the point and the draws consumed are the same; only
+// the owners that failed all of them enter the rounds.
 template <bool kCount>
 __device__ __forceinline__ V3 coop_reject_mixed(bool want, bool disk, Rng &g, CoopSlot *slots, const LdsJump *jt,
-                                                uint32_t lane, Counters &cnt) {
+                                                uint32_t lane, Counters &cnt, int n_local, int n_min) {
     V3 res = (RT_SHADE_LEAN & 16) ? unset_v3() : mk(0, 0, 0);   // read by the requesting lanes only
     bool pending = want;
     const uint32_t K = disk ? 2u : 3u;
     uint64_t U = wballot(pending);
+    if (n_local > 0 && __popcll(U) >= n_min) {   // wave-uniform
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            if (j < n_local) {
+                if (kCount && first_active()) { cnt.w_rius++; cnt.w_local++; }
+                if (pending) {
+                    const uint64_t x1 = lcg_step(g.x), x2 = lcg_step(x1), x3 = lcg_step(x2);
+                    const float pz = disk ? 0.0f : 2.0f * (float)u48x(x3) - 1.0f;
+                    const V3 p = mk(2.0f * (float)u48x(x1) - 1.0f, 2.0f * (float)u48x(x2) - 1.0f, pz);
+                    g.x = disk ? x2 : x3;
+                    if (kCount) cnt.l_rius++;
+                    if ((double)dot(p, p) < 1.0) {
+                        res = p;
+                        pending = false;
+                    }
+                }
+            }
+        }
+        U = wballot(pending);
+    }
     while (U != 0ull) {
         const uint32_t m = (uint32_t)__popcll(U);            // wave-uniform
         const uint32_t inv = kCoop.inv[m];

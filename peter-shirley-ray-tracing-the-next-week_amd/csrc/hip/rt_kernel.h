@@ -59,6 +59,8 @@ struct RtKernelArgs {
     int ball_claim;           //     ... and the busy lanes below which they claim new samples ...
     int ball_park;            //     ... and whether their segments the cell does not decide move to normal waves
     int ball_drain;           //     ... and whether, with the claims exhausted, normal waves leave the ball's pool to them
+    int coop_local;           // shading stage's rejection sampler: candidates a requesting lane tries by itself ...
+    int coop_local_min;       //     ... before the cooperative rounds (0: none), in waves with at least this many requesters
     int lds_nodes;          // 1: BVH2 nodes copied to LDS (RT_LDS_BLOCK workgroups, one per CU)
     int stack_depth;        // traversal stack entries per lane of the LDS variant (BVH depth + 1)
     // camera (camera.h members)

@@ -824,7 +824,19 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         float cu_ = (RT_SHADE_LEAN & 8) ? unset_f() : 0.f, cv_ = (RT_SHADE_LEAN & 8) ? unset_f() : 0.f;   // starting lanes only
         camera_begin(starting, cu_, cv_);
         // material.h:41-47 for the scattering lanes, camera.h:6-12 for the new samples
-        const V3 pt = coop_reject_mixed<kCount>(st.wants_sphere || starting, starting, g, slots, jt, lane, cnt);
+        // (most of a ready batch asks: each lane tries its own first candidates, the rounds serve the rest)
+        const uint64_t trips0 = cnt.w_rius, local0 = cnt.w_local;   // (kCount)
+        const V3 pt = coop_reject_mixed<kCount>(st.wants_sphere || starting, starting, g, slots, jt, lane, cnt,
+                                                A.coop_local, A.coop_local_min);
+        if (kCount && lane == 0) {   // all 64 lanes are active here: lane 0 holds the wave-level trips
+            const uint64_t local = cnt.w_local - local0, rounds = cnt.w_rius - trips0 - local;
+            cnt.sampler[RT_SAMPLER_LOCAL] += local;
+            cnt.sampler[RT_SAMPLER_ROUNDS] += rounds;
+            if (ballrole) {
+                cnt.sampler[RT_SAMPLER_BALL_LOCAL] += local;
+                cnt.sampler[RT_SAMPLER_BALL_ROUNDS] += rounds;
+            }
+        }
         mark(3);
         // a scattered path and a new camera sample (disjoint lanes: a lane that started
         // a sample this iteration was idle, not ready) begin their next segment in ONE
@@ -924,6 +936,9 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         }
     }
 
+    if (kCount && lane == 0)
+        for (int k = 0; k < RT_SAMPLER_N; ++k)
+            if (cnt.sampler[k]) atomicAdd(&A.stats[RT_STAT_SAMPLER + k], (unsigned long long)cnt.sampler[k]);
     if (kCount && kBall && lane == 0)
         for (int k = 0; k < RT_BALL_N; ++k)
             if (cnt.ball[k]) atomicAdd(&A.stats[RT_STAT_BALL + k], (unsigned long long)cnt.ball[k]);

@@ -708,6 +708,13 @@ static int env_int(const char *name, int dflt, int lo, int hi) {
     if (const char *e = std::getenv(name)) return std::max(lo, std::min(hi, std::atoi(e)));
     return dflt;
 }
+// The shading stage's rejection sampler (rt_device.h coop_reject_mixed): candidates each
+// requesting lane tries by itself before the cooperative rounds (RTNW_COOP_LOCAL, 0: none),
+// in waves with at least RTNW_COOP_LOCAL_MIN requesters.  Any setting renders the same image;
+// 2 and 33 against none: c4 48.49 -> 47.21 ms, c3 22.47 -> 21.84, c2 7.85 -> 7.57
+// (profiles/r07/ab_c4.log, ab_c4_sweep.log for the other settings).
+#define RT_COOP_LOCAL 2
+#define RT_COOP_LOCAL_MIN 33
 static int ball_waves() {
     if (const char *e = std::getenv("RTNW_BALL_WAVES")) return std::max(0, std::min(RT_LDS_BLOCK / 64, std::atoi(e)));
     return RT_BALL_WAVES;
@@ -921,6 +928,8 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
     a.ball_claim = env_int("RTNW_BALL_CLAIM", RT_BALL_CLAIM, 1, 64);
     a.ball_park = env_int("RTNW_BALL_PARK", 1, 0, 1);
     a.ball_drain = env_int("RTNW_BALL_DRAIN", 1, 0, 1);
+    a.coop_local = env_int("RTNW_COOP_LOCAL", RT_COOP_LOCAL, 0, 3);
+    a.coop_local_min = env_int("RTNW_COOP_LOCAL_MIN", RT_COOP_LOCAL_MIN, 1, 64);
     a.nprims = (uint32_t)s->nprims;
     a.stack_depth = s->stack_depth;
     a.features = scene_features(s);
@@ -1074,6 +1083,14 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
                              b[RT_BALL_ITERS], b[RT_BALL_ITERS] ? (double)b[RT_BALL_LIVE] / b[RT_BALL_ITERS] : 0.0,
                              b[RT_BALL_ITERS] ? (double)b[RT_BALL_ROUNDS] / b[RT_BALL_ITERS] : 0.0, b[RT_BALL_CELL_BALL],
                              b[RT_BALL_DENIED], stats->segments, b[RT_BALL_PUSH_IN], b[RT_BALL_PUSH_OUT], b[RT_BALL_TAKEN]);
+                unsigned long long r[RT_SAMPLER_N];
+                HIP_TRY(hipMemcpy(r, (unsigned long long *)s->stats + RT_STAT_SAMPLER, sizeof r, hipMemcpyDeviceToHost));
+                std::fprintf(stderr,
+                             "rtnw shading-stage sampler: local trips / iteration %.3f, cooperative rounds / iteration %.3f; "
+                             "ball waves: %.3f and %.3f\n",
+                             w[0] ? (double)r[RT_SAMPLER_LOCAL] / w[0] : 0.0, w[0] ? (double)r[RT_SAMPLER_ROUNDS] / w[0] : 0.0,
+                             b[RT_BALL_ITERS] ? (double)r[RT_SAMPLER_BALL_LOCAL] / b[RT_BALL_ITERS] : 0.0,
+                             b[RT_BALL_ITERS] ? (double)r[RT_SAMPLER_BALL_ROUNDS] / b[RT_BALL_ITERS] : 0.0);
             }
         }
         if (prof) {
