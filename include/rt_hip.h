@@ -260,7 +260,54 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
 int rt_device_alloc(int device, uint64_t bytes, void **out);
 int rt_device_free(void *ptr);
 int rt_copy_to_host(void *dst, const void *src_dev, uint64_t bytes);
+int rt_copy_to_device(void *dst_dev, const void *src, uint64_t bytes);
 int rt_device_count(int *out);
+
+/* ------------------------------------------- moments and adaptive sampling */
+/* rt_render_tiles + per-pixel moments of the work items' channel sums y = (r+g)+b:
+ * moments_dev receives 2 floats per pixel (sum y, sum y*y; float32, item order) in the packed
+ * tile layout.  With RT_FLAG_SUM_IN both out_dev and moments_dev hold the earlier samples'
+ * values on entry.  out_dev is bitwise what rt_render_tiles writes.  The moments are sums
+ * whatever RT_FLAG_SUM_OUT says, and do not depend on the sample batches.  With RT_FLAG_COUNT
+ * or RT_FLAG_PROFILE it returns RT_ERR_INVALID. */
+int rt_render_tiles_moments(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                            const int32_t *tiles, int ntiles, float *out_dev, float *moments_dev,
+                            void *stream, rt_stats *stats);
+
+typedef struct rt_adaptive_params {
+    int32_t min_spp;    /* first pass, every pixel; >= 2 */
+    int32_t step_spp;   /* samples each later pass adds to the pixels still active; >= 1;
+                           the last pass is clipped so that no pixel passes p->spp */
+    float tolerance;    /* relative standard error; <= 0: no pixel ever converges */
+    float floor;        /* >= 0, added to the mean of y: dark pixels converge too */
+} rt_adaptive_params;
+
+typedef struct rt_adaptive_stats {
+    double passes;            /* megakernel passes (the first over every pixel) */
+    double samples;           /* camera samples rendered = the sum of out_spp */
+    double pixels_converged;  /* pixels the rule stopped, those it stopped at the cap included */
+    double pixels_capped;     /* pixels still active after p->spp samples */
+    double kernel_ms, resolve_ms, select_ms;   /* HIP-event times summed over the passes */
+} rt_adaptive_stats;
+
+/* Error-driven render of the w x h rectangle at (x0, y0): every pixel gets min_spp samples,
+ * then step_spp more per pass while it is active, up to p->spp (the cap).  With one sample
+ * per work item (chunk is forced to 1), y = (r+g)+b of a sample, n the pixel's samples so
+ * far, S1 = sum y and S2 = sum y*y (float32 sums in sample order, read as doubles), a pixel
+ * leaves the active set for good after a pass when, in FP64 and in exactly this order,
+ *     N*S2 - S1*S1  <=  ((tol*tol) * (N - 1.0)) * (t*t),   t = S1 + floor*N
+ * i.e. the standard error of the mean of y <= tolerance x (mean of y + floor), with the N-1
+ * sample variance; a NaN moment compares false, and tolerance <= 0 skips the comparison: no
+ * pixel converges.  A pixel that received n samples is bitwise that pixel of
+ * rt_render_tile(spp = n): out_rgb holds sum * float(1.0 / n) with the pixel's own n.
+ * p->spp is the cap.  out_rgb: h*w*3 host floats (mean); out_spp: h*w int32 (may be NULL);
+ * out_moments: h*w*2 floats (may be NULL); stats may be NULL.  Synchronous.
+ * RT_ERR_INVALID for a null argument, min_spp < 2, step_spp < 1, p->spp < min_spp, a negative
+ * or non-finite floor, a NaN tolerance, p->sample_offset != 0 or any of RT_FLAG_COUNT,
+ * RT_FLAG_PROFILE, RT_FLAG_SUM_IN, RT_FLAG_SUM_OUT; RT_FLAG_RIGHT_FOLD passes through. */
+int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                       const rt_adaptive_params *ap, int x0, int y0, int w, int h,
+                       float *out_rgb, int32_t *out_spp, float *out_moments, rt_adaptive_stats *stats);
 
 /* Diagnostic: the device's float transcendentals of the path on n host inputs (out: n
  * floats) — fn 0 the megakernel's sinf (texture.h:36, 55), 2 its asinf and 4 its

@@ -16,6 +16,7 @@
 #include "rt_hip.h"
 #include "../rt_layout.h"
 #include "../hip/rt_kernel.h"
+#include "../hip/rt_moments.h"
 #include "bvh.h"
 #include "rtnw.h"
 
@@ -141,6 +142,9 @@ double algorithmic_bytes(const rt_stats &st, double items, int bvh_width) {
 
 }  // namespace
 
+// rt_moments.hip's launchers, set by that unit's static initialiser (rt_moments.h)
+RtMomentsLaunch rt_moments_launch = {nullptr, nullptr, nullptr};
+
 // shared with dist.cpp: sets the thread-local message rt_last_error() returns
 int rt_internal_fail(int code, const std::string &msg) { return fail(code, msg); }
 
@@ -174,10 +178,15 @@ struct rt_scene {
     std::vector<float> deep_balls;          // dense media's boundary balls (cx, cy, cz, r), rt_scene_create
     uint32_t npix = 0;
     void *job_xy = nullptr, *job_out = nullptr;
+    size_t job_cap = 0;           // pixels job_xy and job_out have room for
     void *slab = nullptr;
     size_t slab_bytes = 0;
     void *acc = nullptr;          // per-pixel running sums between sample batches
     size_t acc_bytes = 0;
+    void *frame = nullptr;        // rt_render_adaptive: the frame's sums, moments, counts and flags ...
+    size_t frame_bytes = 0;
+    void *pin = nullptr;          // ... and pinned host memory for the passes' pixel lists, flags and counters
+    size_t pin_bytes = 0;
     void *fold = nullptr;         // RT_FLAG_RIGHT_FOLD: the lanes' attenuation stacks (rt_kernel.h RtKernelArgs.fold)
     size_t fold_bytes = 0;
     void *counter = nullptr, *stats = nullptr;
@@ -322,8 +331,9 @@ static int validate_desc(const rt_scene_desc *d) {
 void rt_scene_destroy(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    for (void *p : {s->arena, s->job_xy, s->job_out, s->slab, s->acc, s->fold, s->counter, s->host_out})
+    for (void *p : {s->arena, s->job_xy, s->job_out, s->slab, s->acc, s->frame, s->fold, s->counter, s->host_out})
         if (p) (void)hipFree(p);
+    if (s->pin) (void)hipHostFree(s->pin);
     for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
     if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
     delete s;
@@ -807,22 +817,53 @@ static int prepare_job(rt_scene *s, const int32_t *tiles, int ntiles, int nx, in
     if (s->job_xy) { (void)hipFree(s->job_xy); s->job_xy = nullptr; }
     if (s->job_out) { (void)hipFree(s->job_out); s->job_out = nullptr; }
     s->job_tiles.clear();
+    s->job_cap = 0;
     if (int rc = upload(&s->job_xy, xy)) return rc;
     if (int rc = upload(&s->job_out, oi)) return rc;
+    s->job_cap = xy.size();
     s->npix = (uint32_t)xy.size();
     s->job_ndeep = ndeep;
     s->job_tiles = key;
     return RT_OK;
 }
 
-int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
-                    float *out_dev, void *stream_v, rt_stats *stats) {
-    if (!s || !cam || !p || ntiles < 0) return fail(RT_ERR_INVALID, "rt_render_tiles: bad argument");
-    if (ntiles == 0) {   // a rank with no tiles (more ranks than tiles) has nothing to do
-        if (stats) std::memset(stats, 0, sizeof *stats);
-        return RT_OK;
+// A job over any subset of a frame with explicit output slots (rt_render_adaptive's later
+// passes): job pixel k is image pixel xy[k] (x | y << 16) and reads and writes its sums and
+// moments at slot[k] of the caller's full-frame buffers, in place — no gather or scatter
+// copies.  The pixels are claimed in the order given; the caller lists the deep ones first
+// (ndeep of them: a frame's deep pixels are found once, not per pass).  xy and slot are
+// pinned host memory that stays as it is until the job's launches have completed: they are
+// copied on the job's stream, over the previous job's lists when those have the room (the
+// caller has waited for the launches that read them).  Such a job never answers a later
+// tile job's cache lookup: it leaves no key behind.
+struct JobSlots {
+    const uint32_t *xy, *slot;
+    uint32_t n, ndeep;
+};
+static int prepare_job_slots(rt_scene *s, const JobSlots &js, int nx, int ny, hipStream_t stream) {
+    if (js.n == 0 || js.ndeep > js.n || nx > 65535 || ny > 65535) return fail(RT_ERR_INVALID, "empty job or image too large");
+    for (uint32_t i = 0; i < js.n; i++)
+        if ((int)(js.xy[i] & 0xFFFFu) >= nx || (int)(js.xy[i] >> 16) >= ny) return fail(RT_ERR_INVALID, "job pixel outside the image");
+    s->job_tiles.clear();
+    if (!s->job_xy || !s->job_out || js.n > s->job_cap) {
+        if (s->job_xy) { (void)hipFree(s->job_xy); s->job_xy = nullptr; }
+        if (s->job_out) { (void)hipFree(s->job_out); s->job_out = nullptr; }
+        s->job_cap = 0;
+        HIP_TRY(hipMalloc(&s->job_xy, (size_t)js.n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&s->job_out, (size_t)js.n * sizeof(uint32_t)));
+        s->job_cap = js.n;
     }
-    if (!tiles || !out_dev) return fail(RT_ERR_INVALID, "rt_render_tiles: null tiles or output");
+    HIP_TRY(hipMemcpyAsync(s->job_xy, js.xy, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(s->job_out, js.slot, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    s->npix = js.n;
+    s->job_ndeep = js.ndeep == js.n ? 0 : js.ndeep;   // all deep: one group
+    return RT_OK;
+}
+
+// The body of rt_render_tiles and rt_render_tiles_moments: the job is the tile list, or `js`
+// when non-null; with mom_dev the resolve is rt_moments.hip's, which also keeps the moments.
+static int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
+                      const JobSlots *js, float *out_dev, float *mom_dev, void *stream_v, rt_stats *stats) {
     if (p->nx <= 0 || p->ny <= 0 || p->spp <= 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "bad render parameters");
     if (s->has_moving && (cam->time0 < s->time0 || cam->time1 > s->time1))
         return fail(RT_ERR_INVALID, "camera shutter outside the scene's time span (moving-sphere bounds)");
@@ -846,7 +887,8 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
     }
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = (hipStream_t)stream_v;
-    if (int rc = prepare_job(s, tiles, ntiles, p->nx, p->ny, cam)) return rc;
+    if (int rc = js ? prepare_job_slots(s, *js, p->nx, p->ny, stream) : prepare_job(s, tiles, ntiles, p->nx, p->ny, cam))
+        return rc;
 
     // Work item = `chunk` samples of one pixel, one by default: short items keep each
     // wave's lanes on neighbouring pixels (a wave deals its claims to lanes as they free
@@ -1018,8 +1060,13 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
         HIP_TRY(hipEventRecord(s->ev[0], stream));
         HIP_TRY(rt_launch_megakernel(&a, s->grid[mode], fold ? RT_LAUNCH_FOLD : mode, stream));
         HIP_TRY(hipEventRecord(s->ev[1], stream));
-        HIP_TRY(rt_launch_resolve((const float *)s->slab, s->npix, a.nchunks, k, (float4 *)s->acc, rmode,
-                                  (const uint32_t *)s->job_out, out_dev, stream));
+        if (mom_dev)
+            HIP_TRY(rt_moments_launch.resolve((const float *)s->slab, rt_slab_floats(), s->npix, a.nchunks, k,
+                                             (float4 *)s->acc, rmode, (const uint32_t *)s->job_out, out_dev, mom_dev,
+                                             stream));
+        else
+            HIP_TRY(rt_launch_resolve((const float *)s->slab, s->npix, a.nchunks, k, (float4 *)s->acc, rmode,
+                                      (const uint32_t *)s->job_out, out_dev, stream));
         HIP_TRY(hipEventRecord(s->ev[2], stream));
         if (wave_log) {
             std::vector<unsigned long long> h(wave_log_n);   // the render stream may be non-blocking
@@ -1124,6 +1171,218 @@ int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_para
         stats->prescan = (double)s->nprescan;
         stats->stack_depth = (double)(s->lds_nodes ? s->stack_depth : s->bvh_width >= 8 ? RT_STACK_DEPTH_W8 : RT_STACK_DEPTH);
     }
+    return RT_OK;
+}
+
+int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
+                    float *out_dev, void *stream_v, rt_stats *stats) {
+    if (!s || !cam || !p || ntiles < 0) return fail(RT_ERR_INVALID, "rt_render_tiles: bad argument");
+    if (ntiles == 0) {   // a rank with no tiles (more ranks than tiles) has nothing to do
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    if (!tiles || !out_dev) return fail(RT_ERR_INVALID, "rt_render_tiles: null tiles or output");
+    return render_job(s, cam, p, tiles, ntiles, nullptr, out_dev, nullptr, stream_v, stats);
+}
+
+int rt_render_tiles_moments(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles,
+                            int ntiles, float *out_dev, float *moments_dev, void *stream_v, rt_stats *stats) {
+    if (!cam || !p || ntiles < 0) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: bad argument");
+    if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE))
+        return fail(RT_ERR_INVALID, "rt_render_tiles_moments: RT_FLAG_COUNT and RT_FLAG_PROFILE are not supported");
+    if (!s) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: null scene");
+    if (!rt_moments_launch.resolve)
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_tiles_moments: this library was linked without the moments unit (rt_moments.o)");
+    if (ntiles == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    if (!tiles || !out_dev || !moments_dev) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: null tiles, output or moments");
+    return render_job(s, cam, p, tiles, ntiles, nullptr, out_dev, moments_dev, stream_v, stats);
+}
+
+// Adaptive sampling (rt_hip.h).  Every pixel of the frame keeps, in device
+// buffers in slot order (y * w + x), its running sums, its two moments, its sample count
+// and an active flag.  The first pass renders min_spp samples of every pixel; after each
+// pass rt_adaptive_select retires the converged pixels, and the next pass is a job of the
+// pixels still active — 8 x 8 blocks of the frame in raster order, each block column by
+// column, so that a wave's 64 items stay neighbours — which continues their sums and
+// moments in place (RT_FLAG_SUM_IN at sample_offset = the samples they have).  Every
+// active pixel has the same count, so the cap is the host's to check.  The argument checks
+// come before any HIP call.
+int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const rt_adaptive_params *ap,
+                       int x0, int y0, int w, int h, float *out_rgb, int32_t *out_spp, float *out_moments,
+                       rt_adaptive_stats *ast) {
+    if (!cam || !p || !ap || !out_rgb) return fail(RT_ERR_INVALID, "rt_render_adaptive: null argument");
+    if (ap->min_spp < 2) return fail(RT_ERR_INVALID, "rt_render_adaptive: min_spp must be at least 2 (a variance needs two samples)");
+    if (ap->step_spp < 1) return fail(RT_ERR_INVALID, "rt_render_adaptive: step_spp must be at least 1");
+    if (p->spp < ap->min_spp) return fail(RT_ERR_INVALID, "rt_render_adaptive: spp (the cap) is below min_spp");
+    if (!(ap->floor >= 0.0f) || !std::isfinite(ap->floor))
+        return fail(RT_ERR_INVALID, "rt_render_adaptive: floor must be finite and not negative");
+    if (std::isnan(ap->tolerance)) return fail(RT_ERR_INVALID, "rt_render_adaptive: tolerance is NaN");
+    if (p->sample_offset != 0) return fail(RT_ERR_INVALID, "rt_render_adaptive: sample_offset must be 0");
+    if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE | RT_FLAG_SUM_IN | RT_FLAG_SUM_OUT))
+        return fail(RT_ERR_INVALID, "rt_render_adaptive: RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
+    if (w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > 0x7FFFFFFFull) return fail(RT_ERR_INVALID, "rt_render_adaptive: empty or oversized frame");
+    if (!s) return fail(RT_ERR_INVALID, "rt_render_adaptive: null scene");
+    if (!rt_moments_launch.resolve)
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: this library was linked without the moments unit (rt_moments.o)");
+
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
+    hipStream_t stream = s->own_stream;
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;
+    // RTNW_TRACE: where the call's host time went, on stderr (diagnostics)
+    const bool trace_on = std::getenv("RTNW_TRACE") != nullptr;
+    auto clock_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = clock_ms();
+    double t_first = 0, t_jobs = 0, t_lists = 0, t_select = 0;
+    // one allocation, kept with the scene: sums (3 floats), moments (2 floats), counts (int32),
+    // the select's two counters (in 16 B), active flags (1 byte) per pixel
+    const size_t off_mom = (size_t)npix * 12, off_spp = off_mom + (size_t)npix * 8, off_cnt = off_spp + (size_t)npix * 4,
+                 off_act = off_cnt + 16, total = off_act + npix;
+    if (total > s->frame_bytes) {
+        if (s->frame) (void)hipFree(s->frame);
+        s->frame = nullptr;
+        s->frame_bytes = 0;
+        HIP_TRY(hipMalloc(&s->frame, total));
+        s->frame_bytes = total;
+    }
+    // pinned host memory, kept as well: the select's counters (16 B), a pass's pixel list and
+    // its slots (uint32 per pixel each, and one entry of slack), the active flags.  Copies to
+    // and from it are true stream copies; with per-pass pageable vectors instead, the first
+    // HIP allocation of the call after a render of many large passes took 14-30 ms.
+    const size_t pin_total = 16 + ((size_t)npix + 1) * 8 + npix;
+    if (pin_total > s->pin_bytes) {
+        if (s->pin) (void)hipHostFree(s->pin);
+        s->pin = nullptr;
+        s->pin_bytes = 0;
+        HIP_TRY(hipHostMalloc(&s->pin, pin_total, hipHostMallocDefault));
+        s->pin_bytes = pin_total;
+    }
+    uint32_t *c = (uint32_t *)s->pin, *xy = c + 4, *slot = xy + npix + 1;
+    uint8_t *flags = (uint8_t *)(slot + npix + 1);
+    uint8_t *base = (uint8_t *)s->frame;
+    float *sums = (float *)base, *mom = (float *)(base + off_mom);
+    int32_t *spp = (int32_t *)(base + off_spp);
+    uint32_t *counters = (uint32_t *)(base + off_cnt);
+    uint8_t *active = base + off_act;
+    HIP_TRY(hipMemsetAsync(spp, 0, (size_t)npix * 4, stream));
+    HIP_TRY(hipMemsetAsync(active, 1, npix, stream));
+
+    rt_render_params q = *p;
+    q.chunk = 1;
+    q.flags = (p->flags & RT_FLAG_RIGHT_FOLD) | RT_FLAG_SUM_OUT;
+    q.spp = ap->min_spp;
+    q.sample_offset = 0;
+    rt_adaptive_stats st{};
+    rt_stats rs;
+    const int32_t tile[4] = {x0, y0, w, h};
+    if (int rc = render_job(s, cam, &q, tile, 1, nullptr, sums, mom, stream, &rs)) return rc;
+    t_first = clock_ms() - t_begin;
+    st.kernel_ms += rs.kernel_ms;
+    st.resolve_ms += rs.resolve_ms;
+
+    const int cap = p->spp;
+    int done = ap->min_spp, added = ap->min_spp;
+    uint32_t nactive = npix;
+    std::vector<uint8_t> deep;   // the frame's deep pixels (prepare_job's order: they go first)
+    std::vector<uint32_t> rxy, rslot;   // the other active pixels of a pass, appended after the deep ones
+    bool deep_first = !s->deep_balls.empty();
+    if (const char *e = std::getenv("RTNW_DEEP_FIRST")) deep_first = deep_first && std::atoi(e) != 0;
+    for (;;) {
+        st.passes += 1;
+        st.samples += (double)nactive * (double)added;
+        double t0 = clock_ms();
+        HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), stream));
+        HIP_TRY(hipEventRecord(s->ev[0], stream));
+        HIP_TRY(rt_moments_launch.select(npix, added, ap->tolerance, ap->floor, mom, spp, active, counters, stream));
+        HIP_TRY(hipEventRecord(s->ev[1], stream));
+        HIP_TRY(hipMemcpyAsync(c, counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        const bool more = done < cap;
+        if (more) HIP_TRY(hipMemcpyAsync(flags, active, npix, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        st.select_ms += ms;
+        st.pixels_converged += (double)c[1];
+        nactive = c[0];
+        t_select += clock_ms() - t0;
+        if (!more || nactive == 0) break;
+        t0 = clock_ms();
+        if (deep_first && deep.empty()) {
+            deep.resize(npix);
+            for (int yy = 0; yy < h; yy++)
+                for (int xx = 0; xx < w; xx++) deep[(size_t)yy * w + xx] = deep_pixel(s, cam, x0 + xx, y0 + yy, p->nx, p->ny);
+        }
+        // the active pixels, the deep ones first; each group block by block, a block column by
+        // column.  One sweep without a branch on the flags (they are as good as random): every
+        // pixel is written to the end of both lists, and a list grows only if the pixel is its own.
+        uint32_t n = 0, nr = 0;
+        if (deep_first && rxy.empty()) {
+            rxy.resize((size_t)npix + 1);
+            rslot.resize((size_t)npix + 1);
+        }
+        for (int by = 0; by < h; by += 8)
+            for (int bx = 0; bx < w; bx += 8)
+                for (int xx = bx; xx < std::min(bx + 8, w); xx++)
+                    for (int yy = by; yy < std::min(by + 8, h); yy++) {
+                        const uint32_t o = (uint32_t)yy * (uint32_t)w + (uint32_t)xx;
+                        const uint32_t v = (uint32_t)(x0 + xx) | ((uint32_t)(y0 + yy) << 16);
+                        const uint32_t on = flags[o] != 0;
+                        if (deep_first) {
+                            const uint32_t d = deep[o] != 0;
+                            rxy[nr] = v;
+                            rslot[nr] = o;
+                            nr += on & (d ^ 1u);
+                            xy[n] = v;
+                            slot[n] = o;
+                            n += on & d;
+                        } else {
+                            xy[n] = v;
+                            slot[n] = o;
+                            n += on;
+                        }
+                    }
+        const uint32_t ndeep = deep_first ? n : 0;
+        if ((uint64_t)n + nr > npix) return fail(RT_ERR_HIP, "rt_render_adaptive: pixel list overflow");
+        if (nr) {
+            std::memcpy(xy + n, rxy.data(), (size_t)nr * sizeof(uint32_t));
+            std::memcpy(slot + n, rslot.data(), (size_t)nr * sizeof(uint32_t));
+            n += nr;
+        }
+        if (n != nactive) return fail(RT_ERR_HIP, "rt_render_adaptive: the active flags and their count disagree");
+        added = std::min(ap->step_spp, cap - done);
+        q.spp = added;
+        q.sample_offset = (uint32_t)done;
+        q.flags |= RT_FLAG_SUM_IN;
+        const JobSlots js{xy, slot, nactive, ndeep};
+        t_lists += clock_ms() - t0;
+        t0 = clock_ms();
+        if (int rc = render_job(s, cam, &q, nullptr, 0, &js, sums, mom, stream, &rs)) return rc;
+        t_jobs += clock_ms() - t0;
+        st.kernel_ms += rs.kernel_ms;
+        st.resolve_ms += rs.resolve_ms;
+        done += added;
+    }
+    st.pixels_capped = (double)nactive;   // still active at the cap
+    if (out_moments) HIP_TRY(hipMemcpyAsync(out_moments, mom, (size_t)npix * 8, hipMemcpyDeviceToHost, stream));
+    if (out_spp) HIP_TRY(hipMemcpyAsync(out_spp, spp, (size_t)npix * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(rt_moments_launch.finish(npix, spp, sums, stream));
+    HIP_TRY(hipMemcpyAsync(out_rgb, sums, (size_t)npix * 12, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (trace_on)
+        std::fprintf(stderr,
+                     "rt_render_adaptive: %.0f passes, %.3f ms: first pass %.3f, later passes %.3f, their pixel lists %.3f, "
+                     "selects and flag copies %.3f; kernels %.3f, resolves %.3f, select kernels %.3f\n",
+                     st.passes, clock_ms() - t_begin, t_first, t_jobs, t_lists, t_select, st.kernel_ms, st.resolve_ms,
+                     st.select_ms);
+    if (ast) *ast = st;
+    return RT_OK;
+}
+
+int rt_copy_to_device(void *dst_dev, const void *src, uint64_t bytes) {
+    HIP_TRY(hipMemcpy(dst_dev, src, bytes, hipMemcpyHostToDevice));
     return RT_OK;
 }
 

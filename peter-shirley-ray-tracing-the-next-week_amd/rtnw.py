@@ -102,6 +102,19 @@ class RtStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtAdaptiveParams(ctypes.Structure):
+    _fields_ = [("min_spp", ctypes.c_int32), ("step_spp", ctypes.c_int32), ("tolerance", ctypes.c_float),
+                ("floor", ctypes.c_float)]
+
+
+class RtAdaptiveStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "passes", "samples", "pixels_converged", "pixels_capped", "kernel_ms", "resolve_ms", "select_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RtCheckpoint(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("nx", ctypes.c_int32),
                 ("ny", ctypes.c_int32), ("samples_done", ctypes.c_uint32), ("max_depth", ctypes.c_int32),
@@ -134,6 +147,14 @@ def lib():
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, P(RtStats)]),
             "rt_render_tiles": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams), ctypes.c_void_p,
                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, P(RtStats)]),
+            "rt_render_tiles_moments": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams),
+                                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, P(RtStats)]),
+            "rt_render_adaptive": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams),
+                                                  P(RtAdaptiveParams), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  P(RtAdaptiveStats)]),
+            "rt_copy_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
             "rt_device_alloc": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, P(ctypes.c_void_p)]),
             "rt_device_free": (ctypes.c_int, [ctypes.c_void_p]),
             "rt_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
@@ -165,7 +186,8 @@ def lib():
             "rt_last_error": (ctypes.c_char_p, []),
             "rt_version": (ctypes.c_char_p, []),
         }
-        optional = {"rt_math_probe"}   # diagnostics a library built before them lacks (A/B variants)
+        # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries
+        optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_copy_to_device"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -329,6 +351,52 @@ class Scene:
                                      int(t.shape[0]), ctypes.c_void_p(out_dev_ptr), ctypes.c_void_p(stream_ptr),
                                      ctypes.byref(st) if stats else None))
         return st.as_dict()
+
+    def render_tile_moments(self, cam: Camera, params: RtRenderParams, x0, y0, w, h, stats: bool = False, sums=None,
+                            moments=None, device: int = 0):
+        """render_tile plus the tile's moments ([h, w, 2] float32: per pixel the sum and the sum
+        of squares of the work items' y = (r + g) + b; rt_render_tiles_moments).  With
+        RT_FLAG_SUM_IN, `sums` and `moments` hold the earlier samples' values."""
+        L = lib()
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        mom = np.zeros((h, w, 2), dtype=np.float32)
+        sum_in = bool(params.flags & RT_FLAG_SUM_IN)
+        if sum_in:
+            if sums is None or moments is None:
+                raise ValueError("RT_FLAG_SUM_IN needs the running sums and moments")
+            out[...] = np.asarray(sums, np.float32).reshape(h, w, 3)
+            mom[...] = np.asarray(moments, np.float32).reshape(h, w, 2)
+        dev = ctypes.c_void_p()
+        _check(L.rt_device_alloc(device, out.nbytes + mom.nbytes, ctypes.byref(dev)))
+        try:
+            dmom = ctypes.c_void_p(dev.value + out.nbytes)
+            if sum_in:
+                _check(L.rt_copy_to_device(dev, out.ctypes.data, out.nbytes))
+                _check(L.rt_copy_to_device(dmom, mom.ctypes.data, mom.nbytes))
+            tile = (ctypes.c_int32 * 4)(x0, y0, w, h)
+            st = RtStats()
+            _check(L.rt_render_tiles_moments(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), tile, 1, dev, dmom,
+                                             None, ctypes.byref(st)))
+            _check(L.rt_copy_to_host(out.ctypes.data, dev, out.nbytes))
+            _check(L.rt_copy_to_host(mom.ctypes.data, dmom, mom.nbytes))
+        finally:
+            L.rt_device_free(dev)
+        return (out, mom, st.as_dict()) if stats else (out, mom)
+
+    def render_adaptive(self, cam: Camera, params: RtRenderParams, x0, y0, w, h, *, min_spp, step_spp, tolerance,
+                        floor=0.0):
+        """Error-driven render (rt_render_adaptive; params.spp is the cap): returns the mean
+        [h, w, 3], each pixel's sample count [h, w] int32, its moments [h, w, 2] and the
+        rt_adaptive_stats as a dict."""
+        ap = RtAdaptiveParams(min_spp=min_spp, step_spp=step_spp, tolerance=tolerance, floor=floor)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        spp = np.zeros((h, w), dtype=np.int32)
+        mom = np.zeros((h, w, 2), dtype=np.float32)
+        st = RtAdaptiveStats()
+        _check(lib().rt_render_adaptive(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), ctypes.byref(ap),
+                                        x0, y0, w, h, out.ctypes.data, spp.ctypes.data, mom.ctypes.data,
+                                        ctypes.byref(st)))
+        return out, spp, mom, st.as_dict()
 
     def close(self):
         if self.handle:
