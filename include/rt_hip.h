@@ -309,6 +309,71 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
                        const rt_adaptive_params *ap, int x0, int y0, int w, int h,
                        float *out_rgb, int32_t *out_spp, float *out_moments, rt_adaptive_stats *stats);
 
+/* ------------------------------- first-hit features and the denoiser */
+/* Feature buffers of the w x h rectangle at (x0, y0): per pixel the mean, over samples
+ * [sample_offset, sample_offset + spp), of each sample's first surface hit.  Sample k of a
+ * pixel is the camera ray rt_render_tile traces for that sample (same key, jitter, lens and
+ * time draws), and its hit the closest one under the (t, list order) rule:
+ *   albedo   (3)  the hit material's colour: the texture's value at the hit for a lambertian,
+ *                 a diffuse light and an isotropic material, the albedo of a metal, (1, 1, 1)
+ *                 for a dielectric; (1, 1, 1) on a miss
+ *   normal   (3)  the hit record's normal in world space (flip_normals, negative radii and
+ *                 instance chains applied; not normalised again); (0, 0, 0) on a miss
+ *   depth    (1)  t * |direction|; 0 on a miss
+ *   coverage (1)  1 on a hit, 0 on a miss
+ * The samples are added in sample order in float32 and the sum is multiplied by
+ * float(1.0 / spp), as rt_render_tile does with the radiance.  Constant media are ignored: the
+ * features see through them to the surface behind.  Used from p: nx, ny, spp, sample_offset,
+ * seed, t_min; max_depth, background, chunk and RT_FLAG_RIGHT_FOLD are ignored.
+ * RT_ERR_INVALID for a null argument, all four outputs null, nx or ny < 1, spp < 1, a
+ * rectangle outside the image and any of RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN,
+ * RT_FLAG_SUM_OUT (all checked before the device is touched); RT_ERR_UNSUPPORTED on a scene
+ * with a wide BVH (RTNW_BVH_WIDTH 4, 8, 8q).
+ * Host buffers (any of the four may be NULL, not all), row-major h x w.  Synchronous. */
+int rt_render_features(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                       int x0, int y0, int w, int h,
+                       float *albedo, float *normal, float *depth, float *coverage);
+/* The same into device memory, enqueued on `stream` (hipStream_t, NULL = default): 8 floats
+ * per pixel, (albedo.rgb, coverage, normal.xyz, depth), row-major h x w — the guides
+ * rt_denoise_dev reads. */
+int rt_render_features_dev(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                           int x0, int y0, int w, int h, float *guides_dev, void *stream);
+
+typedef struct rt_denoise_params {
+    int32_t iterations;
+    int32_t demodulate;
+    float sigma_color, sigma_depth;
+    int32_t uniform_spp;
+    int32_t pad[3];
+} rt_denoise_params;
+/* rt_denoise_params: iterations 0..8 (0 copies the input); demodulate 0 / 1: filter
+ * colour / max(albedo, 0.01) and multiply the albedo back afterwards; sigma_color, sigma_depth
+ * >= 0 (suggested: 2, 1, with 3 iterations and demodulation); uniform_spp: the
+ * sample count of every pixel when no per-pixel map is given. */
+
+/* Edge-avoiding à-trous wavelet filter (5 x 5 B3-spline taps, 2^i pixels apart in iteration i)
+ * of an nx x ny image.  A tap's weight is the spline's times three edge-stopping terms: the
+ * normals' dot product to the power 128, the relative depth difference (sigma_depth), and —
+ * when moments are given — the luminance difference against the centre pixel's standard error
+ * (sigma_color), from the moments rt_render_tiles_moments / rt_render_adaptive write and each
+ * pixel's sample count (spp map, or uniform_spp when spp is NULL); the variance is filtered
+ * along.  The exact float32 statement is tests/test_denoise_spec.py.  Depths must not be
+ * negative.  Host buffers: color nx*ny*3; albedo, normal, depth as rt_render_features writes
+ * them; moments nx*ny*2 or NULL; spp nx*ny or NULL; out nx*ny*3; *ms (when non-NULL) receives
+ * the kernels' time in ms.  Synchronous.
+ * RT_ERR_INVALID for a null pointer, nx or ny < 1, iterations outside 0..8, a negative or NaN
+ * sigma, and uniform_spp < 1 with moments and no spp map (checked before the device is touched). */
+int rt_denoise(int device, int nx, int ny, const float *color, const float *albedo, const float *normal,
+               const float *depth, const float *moments, const int32_t *spp, const rt_denoise_params *dp,
+               float *out, double *ms);
+/* The same on device buffers, enqueued on `stream`: color_dev 3 floats per pixel (as
+ * rt_render_tiles packs one full-frame tile), guides_dev from rt_render_features_dev,
+ * moments_dev and spp_dev may be NULL.  The filter's planes live in a per-device workspace
+ * that grows on demand: calls on one device must not overlap. */
+int rt_denoise_dev(int device, int nx, int ny, const float *color_dev, const float *guides_dev,
+                   const float *moments_dev, const int32_t *spp_dev, const rt_denoise_params *dp,
+                   float *out_dev, void *stream);
+
 /* Diagnostic: the device's float transcendentals of the path on n host inputs (out: n
  * floats) — fn 0 the megakernel's sinf (texture.h:36, 55), 2 its asinf and 4 its
  * atan2f(a, b) (hitable.h:15-16), all restated from glibc (rt_libm.h); 1, 3, 5 ocml's

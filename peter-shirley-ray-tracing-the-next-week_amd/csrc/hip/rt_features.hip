@@ -1,0 +1,187 @@
+// rt_features.hip — first-hit feature buffers: per pixel the mean albedo, normal, depth and
+// coverage of its camera samples' first surface hits, the guides of the denoiser
+// (rt_denoise.hip).
+//
+//   rt_features           one lane per (pixel, sample): the camera ray the megakernel builds
+//                         for that sample (the same key, jitter draws, lens-disk loop and time
+//                         draw: rt_kernel.hip camera_begin / camera_finish), its closest
+//                         surface hit under hitable_list's (t, key) rule, and the hit's
+//                         material colour, world normal and distance into a slab.
+//   rt_features_resolve   adds a pixel's samples in sample order (float32) and scales the
+//                         sums by float(1.0 / n), as rt_resolve does with the radiance.
+//
+// Constant media are ignored: the features see through them to the surface behind (the
+// subsurface ball's glass shell is final()'s first hit).  Compiled with -ffp-contract=off
+// like the megakernel.
+#include "rt_features.h"
+#include "rt_device.h"
+
+namespace {
+
+// camera.h:41-56 for one sample, sequentially per lane: the draws, in order, are the two
+// jitters, the lens disk's candidates (two draws each, until one is accepted) and the time.
+__device__ __forceinline__ Ray camera_ray(const RtKernelArgs &A, int x, int j, uint32_t sample, uint64_t skey) {
+    Rng g;
+    g.start(sample_key(skey, (uint32_t)(j * A.nx + x), sample), false);
+    const float cu = div_rn((float)((double)x + g.next()), (float)A.nx, A.rnx);   // main.cpp:305-306
+    const float cv = div_rn((float)((double)j + g.next()), (float)A.ny, A.rny);
+    V3 disk;
+    for (;;) {   // camera.h:6-12
+        const bool ok = DiskCand()(g.x, disk);
+        g.skip2();
+        if (ok) break;
+    }
+    CamView C;
+    C.llc = mk(A.llc[0], A.llc[1], A.llc[2]); C.hor = mk(A.hor[0], A.hor[1], A.hor[2]);
+    C.ver = mk(A.ver[0], A.ver[1], A.ver[2]); C.org = mk(A.org[0], A.org[1], A.org[2]);
+    C.cu = mk(A.cu[0], A.cu[1], A.cu[2]); C.cv = mk(A.cv[0], A.cv[1], A.cv[2]);
+    C.t0 = A.ct0; C.t1 = A.ct1; C.lens = A.lens;
+    const V3 rd = scale(C.lens, disk);
+    const V3 offset = add(scale(rd.x, C.cu), scale(rd.y, C.cv));
+    const float span = C.t1 - C.t0;   // camera.h:54; a closed shutter consumes the draw unused
+    double u = 0.0;
+    if (span != 0.0f) u = g.next(); else g.skip();
+    Ray r;
+    r.time = (float)((double)C.t0 + u * (double)span);
+    r.d = sub(sub(add(add(C.llc, scale(cu, C.hor)), scale(cv, C.ver)), C.org), offset);
+    r.o = add(C.org, offset);
+    return r;
+}
+
+// perlin.h:64-74 for one lane, the octaves in the reference's order (coop_turb's values:
+// octave k is noise(q * 2^k) weighted 2^-k, both exact)
+__device__ __forceinline__ float turb_lane(const RtKernelArgs &A, V3 q) {
+    float acc = 0.f, weight = 1.0f;
+#pragma unroll 1
+    for (int k = 0; k < 7; ++k) {
+        const float s = (float)(1u << k);
+        acc += weight * perlin_noise(A.ranvec, A.perm, mk(q.x * s, q.y * s, q.z * s));
+        weight = (float)((double)weight * 0.5);
+    }
+    return fabsf(acc);
+}
+
+// The hit material's colour: its texture's value for the textured kinds (texture.h), the
+// albedo of a metal, white for a dielectric.
+__device__ __forceinline__ V3 material_colour(const RtKernelArgs &A, const Hit &hr) {
+    const float4 m0 = A.mats[hr.mat * 2 + 0], m1 = A.mats[hr.mat * 2 + 1];
+    const int kind = fbits(m0.x);
+    if (kind == RT_MAT_METAL) return mk(m1.x, m1.y, m1.z);
+    if (kind == RT_MAT_DIELECTRIC) return mk(1.0f, 1.0f, 1.0f);
+    if (fbits(m1.w) & 2) return mk(m1.x, m1.y, m1.z);   // a constant texture, resolved by the host
+    float4 t0, t1;
+    const int tkind = tex_leaf<true>(A, fbits(m0.y), hr.p, t0, t1);
+    if (tkind != RT_TEX_NOISE) return tex_value_leaf<true>(A, tkind, t0, t1, hr.u, hr.v);
+    const float nscale = t0.w;                                                  // texture.h:52-56
+    const float sv = 1 + rt_sinf(nscale * hr.p.x + 5 * turb_lane(A, scale(nscale, hr.p)));
+    const float h = 0.5f * 1;
+    return mk(sv * h, sv * h, sv * h);
+}
+
+__global__ __launch_bounds__(RT_BLOCK) void rt_features(const RtKernelArgs A, int x0, int y0, int w,
+                                                        float4 *__restrict__ slab) {
+    __shared__ uint32_t lds_stack[RT_BLOCK / 64][RT_STACK_DEPTH][64];   // [wave][depth][lane], as the megakernel's
+    rtl_lds_init(threadIdx.x);   // rt_libm.h's sine constants (the checker and noise textures)
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t *stk = &lds_stack[wave][0][lane];
+    const uint32_t gid = blockIdx.x * RT_BLOCK + threadIdx.x;
+    const uint32_t total = A.npix * (uint32_t)A.ns;
+    const bool valid = gid < total;   // the lanes past the end stay in the wave, idle
+    const uint32_t it = valid ? gid : 0u;
+    const uint32_t k = it / A.npix, p = it - k * A.npix;
+    const int x = x0 + (int)(p % (uint32_t)w), j = A.ny - 1 - (y0 + (int)(p / (uint32_t)w));
+    const Ray r = camera_ray(A, x, j, A.sample_offset + k, seed_key(A.seed));
+
+    // closest surface hit (hitable_list.h:20-32)
+    float best_t = RT_FLT_MAX;
+    int best_key = 0x7FFFFFFF;
+    uint32_t best_prim = 0xFFFFFFFFu;
+    auto test = [&](uint32_t q) {
+        int key, kind;
+        const float t = prim_t<true>(A.prims, A.insts, q, r, A.tmin, key, kind);
+        keep_closest(true, t, key, q, best_t, best_key, best_prim);
+    };
+    if (A.scan || !A.has_bvh) {   // a flat-scan scene: every primitive (at most RT_SCAN_MAX)
+        const uint32_t n = A.has_bvh ? A.nprims : 0u;
+        if (valid)
+            for (uint32_t q = 0; q < n; ++q) test(q);
+    } else {
+        if (valid)
+            for (uint32_t q = 0; q < (uint32_t)A.nprescan; ++q) test(q);   // kept out of the BVH (capi.cpp)
+        const GlobalNodes gnodes{A.nodes};
+        const Slab sl = make_slab<0>(r, A.tmin);
+        Counters cnt;
+        uint32_t node = A.root;
+        int sp = 0;
+        bool trav = valid;
+        while (wballot(trav) != 0ull) {
+            if (trav) {
+                const uint32_t pleaf = descend<2, false, 1>(gnodes, node, sl, best_t, stk, sp, cnt);
+                if (pleaf != RT_EMPTY_CHILD) {
+                    const uint32_t first = RT_LEAF_FIRST(pleaf), nleaf = RT_LEAF_COUNT(pleaf);
+                    for (uint32_t q = 0; q < nleaf; ++q) test(first + q);
+                }
+                if (node == RT_EMPTY_CHILD) trav = false;   // the stack is empty too (descend pops)
+            }
+        }
+    }
+
+    const bool have = valid && best_prim != 0xFFFFFFFFu;
+    V3 alb = mk(1.0f, 1.0f, 1.0f), nrm = mk(0, 0, 0);
+    float depth = 0.f, cov = 0.f;
+    if (have) {
+        const Hit hr = prim_record<true, true>(A.prims, A.insts, A.mats, best_prim, r, best_t);
+        alb = material_colour(A, hr);
+        nrm = hr.n;
+        depth = best_t * len(r.d);
+        cov = 1.0f;
+    }
+    if (valid) {
+        slab[(size_t)gid * 2 + 0] = make_float4(alb.x, alb.y, alb.z, cov);
+        slab[(size_t)gid * 2 + 1] = make_float4(nrm.x, nrm.y, nrm.z, depth);
+    }
+}
+
+__global__ __launch_bounds__(256) void rt_features_resolve(const float4 *__restrict__ slab, uint32_t npix, int ns, float k,
+                                                           int first, int last, float4 *__restrict__ guides) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f), g = a;
+    if (!first) { a = guides[(size_t)p * 2]; g = guides[(size_t)p * 2 + 1]; }
+#pragma unroll 4
+    for (int c = 0; c < ns; ++c) {   // the loads run ahead; the adds stay in sample order
+        const float4 u = slab[((size_t)c * npix + p) * 2], v = slab[((size_t)c * npix + p) * 2 + 1];
+        a.x = a.x + u.x; a.y = a.y + u.y; a.z = a.z + u.z; a.w = a.w + u.w;
+        g.x = g.x + v.x; g.y = g.y + v.y; g.z = g.z + v.z; g.w = g.w + v.w;
+    }
+    if (last) {
+        a.x = a.x * k; a.y = a.y * k; a.z = a.z * k; a.w = a.w * k;
+        g.x = g.x * k; g.y = g.y * k; g.z = g.z * k; g.w = g.w * k;
+    }
+    guides[(size_t)p * 2] = a;
+    guides[(size_t)p * 2 + 1] = g;
+}
+
+}  // namespace
+
+extern "C" hipError_t rt_launch_features(const RtKernelArgs *a, int x0, int y0, int w, float *slab, hipStream_t stream) {
+    const uint64_t total = (uint64_t)a->npix * (uint64_t)a->ns;
+    if (total == 0) return hipSuccess;
+    if (total >= 0x80000000ull || w <= 0 || a->bvh_width != 2) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)((total + RT_BLOCK - 1) / RT_BLOCK);
+    hipLaunchKernelGGL(rt_features, dim3(blocks), dim3(RT_BLOCK), 0, stream, *a, x0, y0, w, (float4 *)slab);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_features_resolve(const float *slab, uint32_t npix, int ns, float k, int first, int last,
+                                                 float *guides, hipStream_t stream) {
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_features_resolve, dim3((npix + 255) / 256), dim3(256), 0, stream, (const float4 *)slab, npix, ns, k,
+                       first, last, (float4 *)guides);
+    return hipGetLastError();
+}
+
+// the unit announces its launchers to capi.cpp when it is linked in
+static const bool features_unit_linked =
+    (rt_features_launch = RtFeaturesLaunch{rt_launch_features, rt_launch_features_resolve}, true);

@@ -115,6 +115,15 @@ class RtAdaptiveStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtDenoiseParams(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int32), ("demodulate", ctypes.c_int32), ("sigma_color", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float), ("uniform_spp", ctypes.c_int32), ("pad", ctypes.c_int32 * 3)]
+
+
+# the denoiser's suggested settings (DESIGN.md §7c records the sweep that chose them)
+DENOISE_DEFAULTS = dict(iterations=3, demodulate=1, sigma_color=2.0, sigma_depth=1.0)
+
+
 class RtCheckpoint(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("nx", ctypes.c_int32),
                 ("ny", ctypes.c_int32), ("samples_done", ctypes.c_uint32), ("max_depth", ctypes.c_int32),
@@ -155,6 +164,18 @@ def lib():
                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   P(RtAdaptiveStats)]),
             "rt_copy_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
+            "rt_render_features": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams), ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_render_features_dev": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams), ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                      ctypes.c_void_p]),
+            "rt_denoise": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          P(RtDenoiseParams), ctypes.c_void_p, P(ctypes.c_double)]),
+            "rt_denoise_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, P(RtDenoiseParams), ctypes.c_void_p,
+                                              ctypes.c_void_p]),
             "rt_device_alloc": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, P(ctypes.c_void_p)]),
             "rt_device_free": (ctypes.c_int, [ctypes.c_void_p]),
             "rt_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
@@ -186,8 +207,10 @@ def lib():
             "rt_last_error": (ctypes.c_char_p, []),
             "rt_version": (ctypes.c_char_p, []),
         }
-        # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries
-        optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_copy_to_device"}
+        # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
+        # the feature pass and the denoiser
+        optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_copy_to_device",
+                    "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -398,6 +421,24 @@ class Scene:
                                         ctypes.byref(st)))
         return out, spp, mom, st.as_dict()
 
+    def render_features(self, cam: Camera, params: RtRenderParams, x0, y0, w, h):
+        """First-hit feature buffers of the w x h rectangle (rt_render_features): a dict of the
+        per-pixel means over params.spp samples of `albedo` [h, w, 3], `normal` [h, w, 3],
+        `depth` [h, w] and `coverage` [h, w], float32.  Constant media are seen through."""
+        f = dict(albedo=np.zeros((h, w, 3), np.float32), normal=np.zeros((h, w, 3), np.float32),
+                 depth=np.zeros((h, w), np.float32), coverage=np.zeros((h, w), np.float32))
+        _check(lib().rt_render_features(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), x0, y0, w, h,
+                                        f["albedo"].ctypes.data, f["normal"].ctypes.data, f["depth"].ctypes.data,
+                                        f["coverage"].ctypes.data))
+        return f
+
+    def render_features_dev(self, cam: Camera, params: RtRenderParams, x0, y0, w, h, guides_dev_ptr: int,
+                            stream_ptr: int = 0):
+        """rt_render_features_dev: the packed guides (8 floats per pixel: albedo.rgb, coverage,
+        normal.xyz, depth) into device memory, enqueued on the stream."""
+        _check(lib().rt_render_features_dev(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), x0, y0, w, h,
+                                            ctypes.c_void_p(guides_dev_ptr), ctypes.c_void_p(stream_ptr)))
+
     def close(self):
         if self.handle:
             lib().rt_scene_destroy(self.handle)
@@ -408,6 +449,43 @@ class Scene:
             self.close()
         except Exception:
             pass
+
+
+# ------------------------------------------------------------------- denoiser
+def denoise_params(iterations=None, demodulate=None, sigma_color=None, sigma_depth=None, uniform_spp=0):
+    d = DENOISE_DEFAULTS
+    return RtDenoiseParams(iterations=d["iterations"] if iterations is None else iterations,
+                           demodulate=d["demodulate"] if demodulate is None else int(demodulate),
+                           sigma_color=d["sigma_color"] if sigma_color is None else sigma_color,
+                           sigma_depth=d["sigma_depth"] if sigma_depth is None else sigma_depth,
+                           uniform_spp=uniform_spp)
+
+
+def denoise(color, features, moments=None, spp=None, *, iterations=None, demodulate=None, sigma_color=None,
+            sigma_depth=None, device: int = 0, timing: bool = False):
+    """Variance-guided edge-avoiding à-trous filter (rt_denoise) of `color` [ny, nx, 3]:
+    `features` is Scene.render_features' dict (albedo, normal, depth); `moments` [ny, nx, 2]
+    (render_tile_moments / render_adaptive) turns the luminance weight on, with `spp` either
+    a per-pixel int32 map [ny, nx] or one count for every pixel.  Unset settings take
+    DENOISE_DEFAULTS.  Returns the filtered image (and the kernels' ms with timing=True)."""
+    c = np.ascontiguousarray(color, np.float32)
+    ny, nx, _ = c.shape
+    a = np.ascontiguousarray(features["albedo"], np.float32).reshape(ny, nx, 3)
+    n = np.ascontiguousarray(features["normal"], np.float32).reshape(ny, nx, 3)
+    z = np.ascontiguousarray(features["depth"], np.float32).reshape(ny, nx)
+    m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
+    smap, uniform = None, 0
+    if spp is not None and np.ndim(spp) == 0:
+        uniform = int(spp)
+    elif spp is not None:
+        smap = np.ascontiguousarray(spp, np.int32).reshape(ny, nx)
+    dp = denoise_params(iterations, demodulate, sigma_color, sigma_depth, uniform)
+    out = np.zeros_like(c)
+    ms = ctypes.c_double(0.0)
+    _check(lib().rt_denoise(device, nx, ny, c.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,
+                            None if m is None else m.ctypes.data, None if smap is None else smap.ctypes.data,
+                            ctypes.byref(dp), out.ctypes.data, ctypes.byref(ms)))
+    return (out, ms.value) if timing else out
 
 
 # ------------------------------------------------------------ multi-GPU (RCCL)
