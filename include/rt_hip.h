@@ -309,6 +309,28 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
                        const rt_adaptive_params *ap, int x0, int y0, int w, int h,
                        float *out_rgb, int32_t *out_spp, float *out_moments, rt_adaptive_stats *stats);
 
+/* rt_render_adaptive with a neighbourhood guard on the stop rule: same
+ * arguments, checks and outputs, plus guard_radius r in 0..8 (otherwise RT_ERR_INVALID, checked
+ * with the other arguments before the device is touched).  After each pass's samples every
+ * active pixel takes the test above unchanged; fail(q) = q is active and its test fails (a
+ * retired pixel never fails: its moments are frozen and it passed on them).  An active pixel
+ * p leaves the active set iff no pixel q of the rendered rectangle with |qx - px| <= r and
+ * |qy - py| <= r has fail(q): the window is clipped to the w x h rectangle, nothing outside it
+ * exists.  A retired pixel never returns, and at the cap every active pixel stops.  So:
+ *   - r = 0 is rt_render_adaptive bit for bit: image, counts, moments and the stats' passes,
+ *     samples, pixels_converged and pixels_capped;
+ *   - a pixel that received n samples is still bitwise that pixel of rt_render_tile(spp = n);
+ *   - every pixel's count is >= its count under rt_render_adaptive with the same parameters:
+ *     a pixel can only retire after a pass at which its own test passes;
+ *   - tolerance <= 0 is still the fixed render at the cap;
+ *   - a tile is NOT the crop of the frame's result (it is for rt_render_adaptive), since the
+ *     window sees only the rectangle rendered.
+ * pixels_converged counts the pixels that retired, those that retired after the last pass
+ * included; pixels_capped those a failing neighbour (or their own test) still held then. */
+int rt_render_adaptive_guarded(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                               const rt_adaptive_params *ap, int guard_radius, int x0, int y0, int w, int h,
+                               float *out_rgb, int32_t *out_spp, float *out_moments, rt_adaptive_stats *stats);
+
 /* ------------------------------- first-hit features and the denoiser */
 /* Feature buffers of the w x h rectangle at (x0, y0): per pixel the mean, over samples
  * [sample_offset, sample_offset + spp), of each sample's first surface hit.  Sample k of a
@@ -344,12 +366,20 @@ typedef struct rt_denoise_params {
     int32_t demodulate;
     float sigma_color, sigma_depth;
     int32_t uniform_spp;
-    int32_t pad[3];
+    int32_t variance_filter;
+    int32_t pad[2];
 } rt_denoise_params;
 /* rt_denoise_params: iterations 0..8 (0 copies the input); demodulate 0 / 1: filter
  * colour / max(albedo, 0.01) and multiply the albedo back afterwards; sigma_color, sigma_depth
  * >= 0 (suggested: 2, 1, with 3 iterations and demodulation); uniform_spp: the
- * sample count of every pixel when no per-pixel map is given. */
+ * sample count of every pixel when no per-pixel map is given; variance_filter 0 / 1 (any other
+ * value is RT_ERR_INVALID; it took the place of a pad word, so a zeroed struct keeps the
+ * filter of before bit for bit): with 1 and moments present, the luminance weight of every
+ * iteration measures the difference against the 3 x 3 Gaussian (1 2 1 / 4 each way, the direct
+ * neighbours, the centre in place of a neighbour outside the image) of that iteration's input
+ * variance instead of the centre pixel's own (Schied et al. 2017); the variance propagated to
+ * the next iteration is still the unfiltered one's.  Without moments it has no effect.  The
+ * exact statement is tests/test_denoise_varfilter_spec.py. */
 
 /* Edge-avoiding à-trous wavelet filter (5 x 5 B3-spline taps, 2^i pixels apart in iteration i)
  * of an nx x ny image.  A tap's weight is the spline's times three edge-stopping terms: the
@@ -362,7 +392,8 @@ typedef struct rt_denoise_params {
  * them; moments nx*ny*2 or NULL; spp nx*ny or NULL; out nx*ny*3; *ms (when non-NULL) receives
  * the kernels' time in ms.  Synchronous.
  * RT_ERR_INVALID for a null pointer, nx or ny < 1, iterations outside 0..8, a negative or NaN
- * sigma, and uniform_spp < 1 with moments and no spp map (checked before the device is touched). */
+ * sigma, uniform_spp < 1 with moments and no spp map, and a variance_filter other than 0 or 1
+ * (checked before the device is touched). */
 int rt_denoise(int device, int nx, int ny, const float *color, const float *albedo, const float *normal,
                const float *depth, const float *moments, const int32_t *spp, const rt_denoise_params *dp,
                float *out, double *ms);

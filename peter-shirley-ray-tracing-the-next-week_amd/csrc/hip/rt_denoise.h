@@ -17,10 +17,12 @@ extern "C" hipError_t rt_launch_denoise_prepare(uint32_t npix, const float *colo
 // One à-trous iteration with taps `step` pixels apart over the nx x ny planes: E_in -> E_out,
 // or, when out_rgb is non-null (the last iteration), the filtered colour times a' (from
 // guides, as above) to out_rgb, 3 floats per pixel.  use_var: the luminance weight is on
-// (moments were present).
+// (moments were present); variance_filter: with use_var, its denominator takes the 3 x 3
+// Gaussian (1 2 1 / 4, direct neighbours, the centre for those outside the image) of E_in's
+// variance in place of the centre's own.
 extern "C" hipError_t rt_launch_denoise_atrous(int nx, int ny, int step, float sigma_color, float sigma_depth,
-                                               int use_var, const float4 *G, const float4 *E_in, float4 *E_out,
-                                               const float *guides, int demodulate, float *out_rgb,
+                                               int use_var, int variance_filter, const float4 *G, const float4 *E_in,
+                                               float4 *E_out, const float *guides, int demodulate, float *out_rgb,
                                                hipStream_t stream);
 
 // capi.cpp reaches the launchers through this table, filled by rt_denoise.hip's static

@@ -1,6 +1,6 @@
 // rt_denoise.hip — edge-avoiding à-trous wavelet filter guided by the first-hit features
-// and the per-pixel variance (DESIGN.md §7c; Dammertz et al. 2010, with the variance
-// guidance of Schied et al. 2017).
+// and the per-pixel variance (DESIGN.md §7c, §7d; Dammertz et al. 2010, with the variance
+// guidance of Schied et al. 2017 and, on request, their 3 x 3 pre-filter of the variance).
 //
 //   rt_denoise_prepare   packs two float4 planes per pixel: G = (normal.xyz, depth) and
 //                        E = (colour / a', variance of the mean of the demodulated luminance).
@@ -12,7 +12,8 @@
 // Only add, subtract, multiply, IEEE divide, max, min and fabs, compiled with
 // -ffp-contract=off: a fixed sequence of float32 operations, which tests/test_denoise_spec.py
 // restates in numpy and the GPU tests compare bit for bit.  The statement of the filter is
-// that file; the expressions below follow it operation by operation.
+// that file, and tests/test_denoise_varfilter_spec.py for the variance pre-filter; the
+// expressions below follow them operation by operation.
 #include "rt_denoise.h"
 
 namespace {
@@ -46,8 +47,10 @@ __global__ __launch_bounds__(256) void rt_denoise_prepare(uint32_t npix, const f
     E[p] = make_float4(c[0] / a.x, c[1] / a.y, c[2] / a.z, v);
 }
 
-// kVar: the luminance weight (moments were present); kLast: write colour * a' to out_rgb
-template <bool kVar, bool kLast>
+// kVar: the luminance weight (moments were present); kVf: its denominator from the 3 x 3
+// Gaussian of the input variance (rt_denoise_params.variance_filter; only with kVar);
+// kLast: write colour * a' to out_rgb
+template <bool kVar, bool kVf, bool kLast>
 __global__ __launch_bounds__(256) void rt_denoise_atrous(int nx, int ny, int step, float sc2, float sz,
                                                          const float4 *__restrict__ G, const float4 *__restrict__ Ein,
                                                          float4 *__restrict__ Eout, const float4 *__restrict__ guides,
@@ -57,7 +60,23 @@ __global__ __launch_bounds__(256) void rt_denoise_atrous(int nx, int ny, int ste
     const size_t p = (size_t)y * nx + x;
     const float4 Gp = G[p], Ep = Ein[p];
     const float lp = (Ep.x + Ep.y) + Ep.z;
-    const float lden = sc2 * Ep.w + 1e-8f;
+    float vc = Ep.w;
+    if (kVar && kVf) {
+        // SVGF's pre-filter: the direct neighbours whatever `step` is, a neighbour outside the
+        // image replaced by the centre.  The products g * g are powers of two: only the adds round.
+        const float g[3] = {0.25f, 0.5f, 0.25f};
+        vc = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int qx = x + dx, qy = y + dy;
+                const bool in = qx >= 0 && qx < nx && qy >= 0 && qy < ny;
+                vc = vc + (g[dy + 1] * g[dx + 1]) * Ein[in ? (size_t)qy * nx + qx : p].w;
+            }
+        }
+    }
+    const float lden = sc2 * vc + 1e-8f;
     const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float sw = 0.f, sx = 0.f, sy = 0.f, sb = 0.f, sv = 0.f;
 #pragma unroll
@@ -117,18 +136,19 @@ extern "C" hipError_t rt_launch_denoise_prepare(uint32_t npix, const float *colo
 }
 
 extern "C" hipError_t rt_launch_denoise_atrous(int nx, int ny, int step, float sigma_color, float sigma_depth,
-                                               int use_var, const float4 *G, const float4 *E_in, float4 *E_out,
-                                               const float *guides, int demodulate, float *out_rgb,
+                                               int use_var, int variance_filter, const float4 *G, const float4 *E_in,
+                                               float4 *E_out, const float *guides, int demodulate, float *out_rgb,
                                                hipStream_t stream) {
     if (nx <= 0 || ny <= 0) return hipSuccess;
     const dim3 grid((unsigned)((nx + 63) / 64), (unsigned)((ny + 3) / 4)), block(64, 4);
     if (grid.y > 65535u) return hipErrorInvalidValue;
     const float sc2 = sigma_color * sigma_color, sz = sigma_depth * (float)step;
     const float4 *gd = (const float4 *)guides;
-#define RT_DN_LAUNCH(V, L) \
-    hipLaunchKernelGGL((rt_denoise_atrous<V, L>), grid, block, 0, stream, nx, ny, step, sc2, sz, G, E_in, E_out, gd, demodulate, out_rgb)
-    if (use_var) { if (out_rgb) RT_DN_LAUNCH(true, true); else RT_DN_LAUNCH(true, false); }
-    else { if (out_rgb) RT_DN_LAUNCH(false, true); else RT_DN_LAUNCH(false, false); }
+#define RT_DN_LAUNCH(V, F, L) \
+    hipLaunchKernelGGL((rt_denoise_atrous<V, F, L>), grid, block, 0, stream, nx, ny, step, sc2, sz, G, E_in, E_out, gd, demodulate, out_rgb)
+    if (use_var && variance_filter) { if (out_rgb) RT_DN_LAUNCH(true, true, true); else RT_DN_LAUNCH(true, true, false); }
+    else if (use_var) { if (out_rgb) RT_DN_LAUNCH(true, false, true); else RT_DN_LAUNCH(true, false, false); }
+    else { if (out_rgb) RT_DN_LAUNCH(false, false, true); else RT_DN_LAUNCH(false, false, false); }   // no moments: the switch has no effect
 #undef RT_DN_LAUNCH
     return hipGetLastError();
 }

@@ -5,6 +5,9 @@
 //                        same pass over the slab keeps two more running floats per pixel:
 //                        the sum and the sum of squares of the work items' channel sums.
 //   rt_adaptive_select   the convergence decision of rt_render_adaptive (rt_hip.h), FP64.
+//   rt_adaptive_test     the same decision for rt_render_adaptive_guarded: it retires nobody
+//                        and writes a `fail` byte per pixel instead.
+//   rt_adaptive_guard    retires the active pixels whose (2r+1)^2 window holds no failing pixel.
 //   rt_adaptive_finish   each pixel's mean over its own sample count.
 //
 // Compiled with -ffp-contract=off like the megakernel: y * y and the add that follows stay
@@ -80,6 +83,75 @@ __global__ __launch_bounds__(256) void rt_adaptive_select(uint32_t npix, int add
     }
 }
 
+// rt_adaptive_select's decision, kept apart from the retirement: fail[i] = active and not
+// converged, for every pixel of the frame (a retired pixel never fails).  The counts move as
+// in the select; the active flags and the counters are rt_adaptive_guard's to update.
+__global__ __launch_bounds__(256) void rt_adaptive_test(uint32_t npix, int added, float tol, float floor,
+                                                        const float *__restrict__ mom, int32_t *__restrict__ spp,
+                                                        const uint8_t *__restrict__ active, uint8_t *__restrict__ fail) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const bool act = active[i] != 0;
+    bool conv = false;
+    if (act) {
+        const int n = spp[i] + added;
+        spp[i] = n;
+        if (tol > 0.f) {   // tolerance <= 0: never, whatever the moments
+            const double N = (double)n, S1 = (double)mom[2 * (size_t)i], S2 = (double)mom[2 * (size_t)i + 1];
+            const double lhs = N * S2 - S1 * S1;
+            const double t = S1 + (double)floor * N;
+            const double rhs = (((double)tol * (double)tol) * (N - 1.0)) * (t * t);
+            conv = lhs <= rhs;   // a NaN compares false: not converged
+        }
+    }
+    fail[i] = act && !conv;
+}
+
+// The neighbourhood guard: an active pixel leaves the active set iff no pixel of its
+// (2r+1) x (2r+1) window, clipped to the w x h frame, fails.  One lane per pixel, a wave on
+// 64 consecutive pixels of a row, a block on 64 x 4 pixels (rt_denoise.hip's shape).  The
+// block stages its fail bytes and a halo of r in LDS, cells outside the frame as 0; the
+// window's OR is separable: along the rows into `hd`, then down the columns.  At most ten
+// byte loads from global memory per lane (1600 cells over 256 lanes at r = 8) and 6 (2r+1)
+// LDS reads, against (2r+1)^2 global loads for the direct form; no scratch.
+#define RT_GUARD_RMAX 8
+__global__ __launch_bounds__(256) void rt_adaptive_guard(int w, int h, int r, const uint8_t *__restrict__ fail,
+                                                         uint8_t *__restrict__ active, uint32_t *__restrict__ counters) {
+    __shared__ uint8_t tile[4 + 2 * RT_GUARD_RMAX][64 + 2 * RT_GUARD_RMAX];
+    __shared__ uint8_t hd[4 + 2 * RT_GUARD_RMAX][64];
+    const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;
+    const int bx = (int)blockIdx.x * 64, by = (int)blockIdx.y * 4;
+    const int tw = 64 + 2 * r, th = 4 + 2 * r;
+    for (int cy = ty; cy < th; cy += 4) {
+        const int gy = by - r + cy;
+        for (int cx = tx; cx < tw; cx += 64) {
+            const int gx = bx - r + cx;
+            const bool in = gx >= 0 && gx < w && gy >= 0 && gy < h;
+            tile[cy][cx] = in ? fail[(size_t)gy * w + gx] : (uint8_t)0;   // nothing exists outside the frame
+        }
+    }
+    __syncthreads();
+    for (int cy = ty; cy < th; cy += 4) {
+        uint32_t any = 0;
+        for (int k = 0; k <= 2 * r; ++k) any |= tile[cy][tx + k];
+        hd[cy][tx] = (uint8_t)any;
+    }
+    __syncthreads();
+    uint32_t hold = 0;
+    for (int k = 0; k <= 2 * r; ++k) hold |= hd[ty + k][tx];
+    const int x = bx + tx, y = by + ty;
+    const size_t p = (size_t)y * w + x;
+    const bool act = x < w && y < h && active[p] != 0;
+    const bool retire = act && hold == 0;
+    if (retire) active[p] = 0;
+    // one atomic per wave and counter (a wave is a row of the block)
+    const unsigned long long bc = __ballot(retire), ba = __ballot(act && !retire);
+    if (tx == 0) {
+        if (ba) atomicAdd(&counters[0], (uint32_t)__popcll(ba));
+        if (bc) atomicAdd(&counters[1], (uint32_t)__popcll(bc));
+    }
+}
+
 __global__ __launch_bounds__(256) void rt_adaptive_finish(uint32_t npix, const int32_t *__restrict__ spp,
                                                           float *__restrict__ sums) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -114,6 +186,24 @@ extern "C" hipError_t rt_launch_adaptive_select(uint32_t npix, int added, float 
     return hipGetLastError();
 }
 
+extern "C" hipError_t rt_launch_adaptive_test(uint32_t npix, int added, float tol, float floor, const float *mom,
+                                              int32_t *spp, const uint8_t *active, uint8_t *fail, hipStream_t stream) {
+    if (npix == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_adaptive_test, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, added, tol, floor, mom, spp,
+                       active, fail);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_adaptive_guard(int w, int h, int r, const uint8_t *fail, uint8_t *active,
+                                               uint32_t *counters, hipStream_t stream) {
+    if (w <= 0 || h <= 0) return hipSuccess;
+    if (r < 0 || r > RT_GUARD_RMAX) return hipErrorInvalidValue;   // the LDS tile holds a halo of 8
+    const dim3 grid((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)), block(64, 4);
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rt_adaptive_guard, grid, block, 0, stream, w, h, r, fail, active, counters);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t rt_launch_adaptive_finish(uint32_t npix, const int32_t *spp, float *sums, hipStream_t stream) {
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_adaptive_finish, dim3((npix + 255) / 256), dim3(256), 0, stream, npix, spp, sums);
@@ -122,4 +212,6 @@ extern "C" hipError_t rt_launch_adaptive_finish(uint32_t npix, const int32_t *sp
 
 // the unit announces its launchers to capi.cpp when it is linked in
 static const bool moments_unit_linked =
-    (rt_moments_launch = RtMomentsLaunch{rt_launch_resolve_moments, rt_launch_adaptive_select, rt_launch_adaptive_finish}, true);
+    (rt_moments_launch = RtMomentsLaunch{rt_launch_resolve_moments, rt_launch_adaptive_select, rt_launch_adaptive_finish,
+                                         rt_launch_adaptive_test, rt_launch_adaptive_guard},
+     true);

@@ -145,7 +145,7 @@ double algorithmic_bytes(const rt_stats &st, double items, int bvh_width) {
 }  // namespace
 
 // rt_moments.hip's launchers, set by that unit's static initialiser (rt_moments.h)
-RtMomentsLaunch rt_moments_launch = {nullptr, nullptr, nullptr};
+RtMomentsLaunch rt_moments_launch = {nullptr, nullptr, nullptr, nullptr, nullptr};
 // the same for rt_features.hip and rt_denoise.hip (rt_features.h, rt_denoise.h)
 RtFeaturesLaunch rt_features_launch = {nullptr, nullptr};
 RtDenoiseLaunch rt_denoise_launch = {nullptr, nullptr};
@@ -1214,24 +1214,29 @@ int rt_render_tiles_moments(rt_scene *s, const rt_camera_desc *cam, const rt_ren
 // column, so that a wave's 64 items stay neighbours — which continues their sums and
 // moments in place (RT_FLAG_SUM_IN at sample_offset = the samples they have).  Every
 // active pixel has the same count, so the cap is the host's to check.  The argument checks
-// come before any HIP call.
-int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const rt_adaptive_params *ap,
-                       int x0, int y0, int w, int h, float *out_rgb, int32_t *out_spp, float *out_moments,
-                       rt_adaptive_stats *ast) {
-    if (!cam || !p || !ap || !out_rgb) return fail(RT_ERR_INVALID, "rt_render_adaptive: null argument");
-    if (ap->min_spp < 2) return fail(RT_ERR_INVALID, "rt_render_adaptive: min_spp must be at least 2 (a variance needs two samples)");
-    if (ap->step_spp < 1) return fail(RT_ERR_INVALID, "rt_render_adaptive: step_spp must be at least 1");
-    if (p->spp < ap->min_spp) return fail(RT_ERR_INVALID, "rt_render_adaptive: spp (the cap) is below min_spp");
+// come before any HIP call.  rt_render_adaptive and rt_render_adaptive_guarded share this
+// body: with `guarded`, rt_adaptive_test marks the active pixels that fail their own test and
+// rt_adaptive_guard retires an active pixel only if no pixel of its window, clipped to the
+// rectangle, is marked.
+static int render_adaptive(const char *fn, rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                           const rt_adaptive_params *ap, bool guarded, int guard_radius, int x0, int y0, int w, int h,
+                           float *out_rgb, int32_t *out_spp, float *out_moments, rt_adaptive_stats *ast) {
+    const std::string f(fn);
+    if (!cam || !p || !ap || !out_rgb) return fail(RT_ERR_INVALID, f + ": null argument");
+    if (ap->min_spp < 2) return fail(RT_ERR_INVALID, f + ": min_spp must be at least 2 (a variance needs two samples)");
+    if (ap->step_spp < 1) return fail(RT_ERR_INVALID, f + ": step_spp must be at least 1");
+    if (p->spp < ap->min_spp) return fail(RT_ERR_INVALID, f + ": spp (the cap) is below min_spp");
     if (!(ap->floor >= 0.0f) || !std::isfinite(ap->floor))
-        return fail(RT_ERR_INVALID, "rt_render_adaptive: floor must be finite and not negative");
-    if (std::isnan(ap->tolerance)) return fail(RT_ERR_INVALID, "rt_render_adaptive: tolerance is NaN");
-    if (p->sample_offset != 0) return fail(RT_ERR_INVALID, "rt_render_adaptive: sample_offset must be 0");
+        return fail(RT_ERR_INVALID, f + ": floor must be finite and not negative");
+    if (std::isnan(ap->tolerance)) return fail(RT_ERR_INVALID, f + ": tolerance is NaN");
+    if (p->sample_offset != 0) return fail(RT_ERR_INVALID, f + ": sample_offset must be 0");
     if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE | RT_FLAG_SUM_IN | RT_FLAG_SUM_OUT))
-        return fail(RT_ERR_INVALID, "rt_render_adaptive: RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
-    if (w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > 0x7FFFFFFFull) return fail(RT_ERR_INVALID, "rt_render_adaptive: empty or oversized frame");
-    if (!s) return fail(RT_ERR_INVALID, "rt_render_adaptive: null scene");
+        return fail(RT_ERR_INVALID, f + ": RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
+    if (w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > 0x7FFFFFFFull) return fail(RT_ERR_INVALID, f + ": empty or oversized frame");
+    if (guarded && (guard_radius < 0 || guard_radius > 8)) return fail(RT_ERR_INVALID, f + ": guard_radius must be in 0..8");
+    if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
     if (!rt_moments_launch.resolve)
-        return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: this library was linked without the moments unit (rt_moments.o)");
+        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the moments unit (rt_moments.o)");
 
     HIP_TRY(hipSetDevice(s->device));
     if (!s->own_stream) HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
@@ -1243,9 +1248,10 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
     const double t_begin = clock_ms();
     double t_first = 0, t_jobs = 0, t_lists = 0, t_select = 0;
     // one allocation, kept with the scene: sums (3 floats), moments (2 floats), counts (int32),
-    // the select's two counters (in 16 B), active flags (1 byte) per pixel
+    // the select's two counters (in 16 B), active flags (1 byte) per pixel and, for the guard,
+    // fail flags (1 byte)
     const size_t off_mom = (size_t)npix * 12, off_spp = off_mom + (size_t)npix * 8, off_cnt = off_spp + (size_t)npix * 4,
-                 off_act = off_cnt + 16, total = off_act + npix;
+                 off_act = off_cnt + 16, off_fail = off_act + npix, total = off_fail + (guarded ? npix : 0);
     if (total > s->frame_bytes) {
         if (s->frame) (void)hipFree(s->frame);
         s->frame = nullptr;
@@ -1271,7 +1277,7 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
     float *sums = (float *)base, *mom = (float *)(base + off_mom);
     int32_t *spp = (int32_t *)(base + off_spp);
     uint32_t *counters = (uint32_t *)(base + off_cnt);
-    uint8_t *active = base + off_act;
+    uint8_t *active = base + off_act, *failing = base + off_fail;
     HIP_TRY(hipMemsetAsync(spp, 0, (size_t)npix * 4, stream));
     HIP_TRY(hipMemsetAsync(active, 1, npix, stream));
 
@@ -1301,7 +1307,12 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
         double t0 = clock_ms();
         HIP_TRY(hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), stream));
         HIP_TRY(hipEventRecord(s->ev[0], stream));
-        HIP_TRY(rt_moments_launch.select(npix, added, ap->tolerance, ap->floor, mom, spp, active, counters, stream));
+        if (guarded) {   // the own-pixel test for everyone, then the windows
+            HIP_TRY(rt_moments_launch.test(npix, added, ap->tolerance, ap->floor, mom, spp, active, failing, stream));
+            HIP_TRY(rt_moments_launch.guard(w, h, guard_radius, failing, active, counters, stream));
+        } else {
+            HIP_TRY(rt_moments_launch.select(npix, added, ap->tolerance, ap->floor, mom, spp, active, counters, stream));
+        }
         HIP_TRY(hipEventRecord(s->ev[1], stream));
         HIP_TRY(hipMemcpyAsync(c, counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         const bool more = done < cap;
@@ -1350,13 +1361,13 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
                         }
                     }
         const uint32_t ndeep = deep_first ? n : 0;
-        if ((uint64_t)n + nr > npix) return fail(RT_ERR_HIP, "rt_render_adaptive: pixel list overflow");
+        if ((uint64_t)n + nr > npix) return fail(RT_ERR_HIP, f + ": pixel list overflow");
         if (nr) {
             std::memcpy(xy + n, rxy.data(), (size_t)nr * sizeof(uint32_t));
             std::memcpy(slot + n, rslot.data(), (size_t)nr * sizeof(uint32_t));
             n += nr;
         }
-        if (n != nactive) return fail(RT_ERR_HIP, "rt_render_adaptive: the active flags and their count disagree");
+        if (n != nactive) return fail(RT_ERR_HIP, f + ": the active flags and their count disagree");
         added = std::min(ap->step_spp, cap - done);
         q.spp = added;
         q.sample_offset = (uint32_t)done;
@@ -1378,12 +1389,25 @@ int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
     HIP_TRY(hipStreamSynchronize(stream));
     if (trace_on)
         std::fprintf(stderr,
-                     "rt_render_adaptive: %.0f passes, %.3f ms: first pass %.3f, later passes %.3f, their pixel lists %.3f, "
+                     "%s: %.0f passes, %.3f ms: first pass %.3f, later passes %.3f, their pixel lists %.3f, "
                      "selects and flag copies %.3f; kernels %.3f, resolves %.3f, select kernels %.3f\n",
-                     st.passes, clock_ms() - t_begin, t_first, t_jobs, t_lists, t_select, st.kernel_ms, st.resolve_ms,
+                     fn, st.passes, clock_ms() - t_begin, t_first, t_jobs, t_lists, t_select, st.kernel_ms, st.resolve_ms,
                      st.select_ms);
     if (ast) *ast = st;
     return RT_OK;
+}
+
+int rt_render_adaptive(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const rt_adaptive_params *ap,
+                       int x0, int y0, int w, int h, float *out_rgb, int32_t *out_spp, float *out_moments,
+                       rt_adaptive_stats *ast) {
+    return render_adaptive("rt_render_adaptive", s, cam, p, ap, false, 0, x0, y0, w, h, out_rgb, out_spp, out_moments, ast);
+}
+
+int rt_render_adaptive_guarded(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p,
+                               const rt_adaptive_params *ap, int guard_radius, int x0, int y0, int w, int h,
+                               float *out_rgb, int32_t *out_spp, float *out_moments, rt_adaptive_stats *ast) {
+    return render_adaptive("rt_render_adaptive_guarded", s, cam, p, ap, true, guard_radius, x0, y0, w, h, out_rgb, out_spp,
+                           out_moments, ast);
 }
 
 int rt_copy_to_device(void *dst_dev, const void *src, uint64_t bytes) {
@@ -1551,6 +1575,8 @@ static int denoise_check(const char *fn, int nx, int ny, bool nulls, const rt_de
     if (!(dp->sigma_depth >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_depth must not be negative or NaN");
     if (moments && !spp && dp->uniform_spp < 1)
         return fail(RT_ERR_INVALID, f + ": uniform_spp must be at least 1 when moments come without an spp map");
+    if (dp->variance_filter != 0 && dp->variance_filter != 1)
+        return fail(RT_ERR_INVALID, f + ": variance_filter must be 0 or 1");
     if (!rt_denoise_launch.prepare)
         return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the denoise unit (rt_denoise.o)");
     return RT_OK;
@@ -1588,8 +1614,9 @@ static int denoise_run(int device, int nx, int ny, const float *color, const flo
                                       E[0], stream));
     for (int i = 0; i < dp->iterations; i++) {
         const bool last = i + 1 == dp->iterations;
-        HIP_TRY(rt_denoise_launch.atrous(nx, ny, 1 << i, dp->sigma_color, dp->sigma_depth, moments != nullptr, G, E[i & 1],
-                                         E[(i + 1) & 1], guides, dp->demodulate != 0, last ? out : nullptr, stream));
+        HIP_TRY(rt_denoise_launch.atrous(nx, ny, 1 << i, dp->sigma_color, dp->sigma_depth, moments != nullptr,
+                                         dp->variance_filter, G, E[i & 1], E[(i + 1) & 1], guides, dp->demodulate != 0,
+                                         last ? out : nullptr, stream));
     }
     return RT_OK;
 }

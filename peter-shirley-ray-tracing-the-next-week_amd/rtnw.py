@@ -117,7 +117,8 @@ class RtAdaptiveStats(ctypes.Structure):
 
 class RtDenoiseParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int32), ("demodulate", ctypes.c_int32), ("sigma_color", ctypes.c_float),
-                ("sigma_depth", ctypes.c_float), ("uniform_spp", ctypes.c_int32), ("pad", ctypes.c_int32 * 3)]
+                ("sigma_depth", ctypes.c_float), ("uniform_spp", ctypes.c_int32), ("variance_filter", ctypes.c_int32),
+                ("pad", ctypes.c_int32 * 2)]
 
 
 # the denoiser's suggested settings (DESIGN.md §7c records the sweep that chose them)
@@ -163,6 +164,10 @@ def lib():
                                                   P(RtAdaptiveParams), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   P(RtAdaptiveStats)]),
+            "rt_render_adaptive_guarded": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams),
+                                                          P(RtAdaptiveParams), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, P(RtAdaptiveStats)]),
             "rt_copy_to_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
             "rt_render_features": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtRenderParams), ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -209,7 +214,8 @@ def lib():
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
         # the feature pass and the denoiser
-        optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_copy_to_device",
+        optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
+                    "rt_copy_to_device",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
@@ -407,18 +413,25 @@ class Scene:
         return (out, mom, st.as_dict()) if stats else (out, mom)
 
     def render_adaptive(self, cam: Camera, params: RtRenderParams, x0, y0, w, h, *, min_spp, step_spp, tolerance,
-                        floor=0.0):
+                        floor=0.0, guard_radius=None):
         """Error-driven render (rt_render_adaptive; params.spp is the cap): returns the mean
         [h, w, 3], each pixel's sample count [h, w] int32, its moments [h, w, 2] and the
-        rt_adaptive_stats as a dict."""
+        rt_adaptive_stats as a dict.  guard_radius: None, or 0..8 for
+        rt_render_adaptive_guarded: a pixel stops only when no pixel within that many pixels
+        of it, inside the rectangle, fails its own test."""
         ap = RtAdaptiveParams(min_spp=min_spp, step_spp=step_spp, tolerance=tolerance, floor=floor)
         out = np.zeros((h, w, 3), dtype=np.float32)
         spp = np.zeros((h, w), dtype=np.int32)
         mom = np.zeros((h, w, 2), dtype=np.float32)
         st = RtAdaptiveStats()
-        _check(lib().rt_render_adaptive(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), ctypes.byref(ap),
-                                        x0, y0, w, h, out.ctypes.data, spp.ctypes.data, mom.ctypes.data,
-                                        ctypes.byref(st)))
+        if guard_radius is None:
+            _check(lib().rt_render_adaptive(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), ctypes.byref(ap),
+                                            x0, y0, w, h, out.ctypes.data, spp.ctypes.data, mom.ctypes.data,
+                                            ctypes.byref(st)))
+        else:
+            _check(lib().rt_render_adaptive_guarded(self.handle, ctypes.byref(cam.desc), ctypes.byref(params),
+                                                    ctypes.byref(ap), int(guard_radius), x0, y0, w, h, out.ctypes.data,
+                                                    spp.ctypes.data, mom.ctypes.data, ctypes.byref(st)))
         return out, spp, mom, st.as_dict()
 
     def render_features(self, cam: Camera, params: RtRenderParams, x0, y0, w, h):
@@ -452,22 +465,24 @@ class Scene:
 
 
 # ------------------------------------------------------------------- denoiser
-def denoise_params(iterations=None, demodulate=None, sigma_color=None, sigma_depth=None, uniform_spp=0):
+def denoise_params(iterations=None, demodulate=None, sigma_color=None, sigma_depth=None, uniform_spp=0,
+                   variance_filter=0):
     d = DENOISE_DEFAULTS
     return RtDenoiseParams(iterations=d["iterations"] if iterations is None else iterations,
                            demodulate=d["demodulate"] if demodulate is None else int(demodulate),
                            sigma_color=d["sigma_color"] if sigma_color is None else sigma_color,
                            sigma_depth=d["sigma_depth"] if sigma_depth is None else sigma_depth,
-                           uniform_spp=uniform_spp)
+                           uniform_spp=uniform_spp, variance_filter=int(variance_filter))
 
 
 def denoise(color, features, moments=None, spp=None, *, iterations=None, demodulate=None, sigma_color=None,
-            sigma_depth=None, device: int = 0, timing: bool = False):
+            sigma_depth=None, variance_filter=0, device: int = 0, timing: bool = False):
     """Variance-guided edge-avoiding à-trous filter (rt_denoise) of `color` [ny, nx, 3]:
     `features` is Scene.render_features' dict (albedo, normal, depth); `moments` [ny, nx, 2]
     (render_tile_moments / render_adaptive) turns the luminance weight on, with `spp` either
-    a per-pixel int32 map [ny, nx] or one count for every pixel.  Unset settings take
-    DENOISE_DEFAULTS.  Returns the filtered image (and the kernels' ms with timing=True)."""
+    a per-pixel int32 map [ny, nx] or one count for every pixel; variance_filter=1 measures
+    that weight against the 3 x 3 Gaussian of the variance instead of the centre's own.
+    Unset settings take DENOISE_DEFAULTS.  Returns the filtered image (and the kernels' ms with timing=True)."""
     c = np.ascontiguousarray(color, np.float32)
     ny, nx, _ = c.shape
     a = np.ascontiguousarray(features["albedo"], np.float32).reshape(ny, nx, 3)
@@ -479,7 +494,7 @@ def denoise(color, features, moments=None, spp=None, *, iterations=None, demodul
         uniform = int(spp)
     elif spp is not None:
         smap = np.ascontiguousarray(spp, np.int32).reshape(ny, nx)
-    dp = denoise_params(iterations, demodulate, sigma_color, sigma_depth, uniform)
+    dp = denoise_params(iterations, demodulate, sigma_color, sigma_depth, uniform, variance_filter)
     out = np.zeros_like(c)
     ms = ctypes.c_double(0.0)
     _check(lib().rt_denoise(device, nx, ny, c.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,

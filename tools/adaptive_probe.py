@@ -14,7 +14,8 @@ For each configuration (bench.py's c4: final() 500x500, cap 1000; c3: random_mot
 
 Tolerance 0 is the overhead row: no pixel converges, every pixel gets the cap, the image is
 the fixed render's bit for bit (asserted), and the extra time is the passes' launches and
-selects.  Writes <out>/adaptive_probe.json and <out>/adaptive_probe.md.  Not run by any test.
+selects.  --guard-radius adds rt_render_adaptive_guarded at each radius listed ("none" is
+rt_render_adaptive itself).  Writes <out>/adaptive_probe.json and <out>/adaptive_probe.md.  Not run by any test.
 """
 import argparse
 import ctypes
@@ -45,12 +46,14 @@ def main():
     ap.add_argument("--min-spp", type=int, default=32)
     ap.add_argument("--step-spp", type=int, default=64)
     ap.add_argument("--floor", type=float, default=0.01)
+    ap.add_argument("--guard-radius", default="none", help="comma-separated: none (rt_render_adaptive) or 0..8")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--scale", type=float, default=1.0, help="scales the image side and the cap (rehearsals)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08"))
     args = ap.parse_args()
-    tols = [float(t) for t in args.tolerances.split(",")]
+    radii = [None if r == "none" else int(r) for r in args.guard_radius.split(",")]
+    tols = [(float(t), r) for t in args.tolerances.split(",") for r in radii]   # a variant: (tolerance, radius)
     os.makedirs(args.out, exist_ok=True)
     rows = []
     for cfg in args.configs.split(","):
@@ -77,12 +80,18 @@ def main():
             assert rc == 0, L.rt_last_error()
             return ms, buf_img.copy(), st.as_dict()
 
-        def adaptive(tol):
+        def adaptive(variant):
+            tol, radius = variant
             ap_ = rtnw.RtAdaptiveParams(min_spp=args.min_spp, step_spp=args.step_spp, tolerance=tol, floor=args.floor)
             st = rtnw.RtAdaptiveStats()
             t0 = time.perf_counter()
-            rc = L.rt_render_adaptive(scene.handle, ctypes.byref(cam.desc), ctypes.byref(p), ctypes.byref(ap_), 0, 0, nx, ny,
-                                      buf_img.ctypes.data, buf_spp.ctypes.data, buf_mom.ctypes.data, ctypes.byref(st))
+            if radius is None:
+                rc = L.rt_render_adaptive(scene.handle, ctypes.byref(cam.desc), ctypes.byref(p), ctypes.byref(ap_), 0, 0, nx,
+                                          ny, buf_img.ctypes.data, buf_spp.ctypes.data, buf_mom.ctypes.data, ctypes.byref(st))
+            else:
+                rc = L.rt_render_adaptive_guarded(scene.handle, ctypes.byref(cam.desc), ctypes.byref(p), ctypes.byref(ap_),
+                                                  radius, 0, 0, nx, ny, buf_img.ctypes.data, buf_spp.ctypes.data,
+                                                  buf_mom.ctypes.data, ctypes.byref(st))
             ms = (time.perf_counter() - t0) * 1e3
             assert rc == 0, L.rt_last_error()
             return ms, buf_img.copy(), buf_spp.copy(), st.as_dict()
@@ -104,16 +113,17 @@ def main():
         print(f"{cfg}: {scene_name}() {nx}x{ny}, cap {cap}: fixed rt_render_tile {fixed_ms:.2f} ms wall "
               f"(min {min(t_fixed):.2f}, max {max(t_fixed):.2f}; kernel {st_f['kernel_ms']:.2f} ms), "
               f"gamma RMS vs {4 * cap} spp {rms_fixed:.5f}", flush=True)
-        for tol in tols:
-            img, spp, st = last[tol]
+        for variant in tols:
+            tol, radius = variant
+            img, spp, st = last[variant]
             if tol <= 0:
                 assert np.array_equal(img.view(np.uint32), img_f.view(np.uint32)), "tolerance 0 is not the fixed render"
-            ms = statistics.median(t_adapt[tol])
-            row = {"config": cfg, "scene": scene_name, "nx": nx, "ny": ny, "cap": cap, "min_spp": args.min_spp,
+            ms = statistics.median(t_adapt[variant])
+            row = {"guard_radius": radius, "select_ms_per_pass": st["select_ms"] / st["passes"], "config": cfg, "scene": scene_name, "nx": nx, "ny": ny, "cap": cap, "min_spp": args.min_spp,
                    "step_spp": args.step_spp, "floor": args.floor, "tolerance": tol, "rounds": args.rounds,
                    "samples": st["samples"], "samples_share": st["samples"] / (nx * ny * cap), "passes": st["passes"],
                    "pixels_converged": st["pixels_converged"], "pixels_capped": st["pixels_capped"],
-                   "adaptive_ms": ms, "adaptive_ms_min": min(t_adapt[tol]), "adaptive_ms_max": max(t_adapt[tol]),
+                   "adaptive_ms": ms, "adaptive_ms_min": min(t_adapt[variant]), "adaptive_ms_max": max(t_adapt[variant]),
                    "fixed_ms": fixed_ms, "fixed_ms_min": min(t_fixed), "fixed_ms_max": max(t_fixed),
                    "kernel_ms": st["kernel_ms"], "resolve_ms": st["resolve_ms"], "select_ms": st["select_ms"],
                    "fixed_kernel_ms": st_f["kernel_ms"], "fixed_resolve_ms": st_f["resolve_ms"],
@@ -126,12 +136,12 @@ def main():
     with open(os.path.join(args.out, "adaptive_probe.json"), "w") as f:
         json.dump({"tool": "tools/adaptive_probe.py", "args": vars(args), "rows": rows}, f, indent=1)
     with open(os.path.join(args.out, "adaptive_probe.md"), "w") as f:
-        f.write("| config | tolerance | samples (share of cap) | passes | converged / capped pixels | adaptive ms | "
+        f.write("| config | tolerance | guard | samples (share of cap) | passes | converged / capped pixels | adaptive ms | "
                 "fixed ms | kernel / resolve / select ms | gamma RMS adaptive | gamma RMS fixed |\n")
-        f.write("|---|---|---|---|---|---|---|---|---|---|\n")
+        f.write("|---|---|---|---|---|---|---|---|---|---|---|\n")
         for r in rows:
             f.write(f"| {r['config']} {r['scene']} {r['nx']}x{r['ny']} cap {r['cap']} | {r['tolerance']:g} | "
-                    f"{r['samples']:.0f} ({r['samples_share']:.3f}) | {r['passes']:.0f} | "
+                    f"{'none' if r['guard_radius'] is None else r['guard_radius']} | {r['samples']:.0f} ({r['samples_share']:.3f}) | {r['passes']:.0f} | "
                     f"{r['pixels_converged']:.0f} / {r['pixels_capped']:.0f} | {r['adaptive_ms']:.2f} | "
                     f"{r['fixed_ms']:.2f} | {r['kernel_ms']:.2f} / {r['resolve_ms']:.2f} / {r['select_ms']:.2f} | "
                     f"{r['rms_adaptive']:.5f} | {r['rms_fixed']:.5f} |\n")

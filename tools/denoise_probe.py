@@ -12,6 +12,8 @@ step_spp 64, floor 0.01, tolerance 0.05; its moments and count map), and reports
   * the gamma-space RMS against an independent fixed render at 4 x the cap with another seed,
     before and after the filter.
 
+--variance-filter 1 adds every row once more with rt_denoise_params.variance_filter on, and
+--guard-radius R renders the adaptive input with rt_render_adaptive_guarded.
 --sweep adds the grid over sigma_color, sigma_depth and iterations that chose the defaults
 (rtnw.DENOISE_DEFAULTS): the gamma RMS of every setting on all four inputs.
 --timing adds the denoiser's kernel ms for 1..5 iterations (the first figure holds the prepare
@@ -71,6 +73,8 @@ def main():
     ap.add_argument("--step-spp", type=int, default=64)
     ap.add_argument("--floor", type=float, default=0.01)
     ap.add_argument("--feature-spp", type=int, default=16)
+    ap.add_argument("--variance-filter", type=int, default=0, choices=(0, 1), help="1: rows with the pre-filter too")
+    ap.add_argument("--guard-radius", type=int, default=None, help="the adaptive input's guard radius (0..8)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--scale", type=float, default=1.0, help="scales the image side and the cap (rehearsals)")
@@ -97,7 +101,8 @@ def main():
 
         def adaptive():
             color, spp, mom, st = scene.render_adaptive(cam, p, 0, 0, nx, ny, min_spp=args.min_spp, step_spp=args.step_spp,
-                                                        tolerance=args.tolerance, floor=args.floor)
+                                                        tolerance=args.tolerance, floor=args.floor,
+                                                        guard_radius=args.guard_radius)
             return color, mom, spp, st["samples"]
 
         def feats():
@@ -127,11 +132,21 @@ def main():
                    "samples": samples, "samples_share": samples / (nx * ny * cap), **rtnw.DENOISE_DEFAULTS,
                    "render_ms": statistics.median(t[name]), "features_ms": feat_ms,
                    "denoise_ms": statistics.median(t["denoise_" + name]), "denoise_kernel_ms": statistics.median(kms[name]),
-                   "rms_raw": gamma_rms(color, ref), "rms_denoised": gamma_rms(out, ref)}
+                   "rms_raw": gamma_rms(color, ref), "rms_denoised": gamma_rms(out, ref), "variance_filter": 0,
+                   "guard_radius": args.guard_radius if name == "adaptive" else None}
             row["total_raw_ms"] = row["render_ms"]
             row["total_denoised_ms"] = row["render_ms"] + row["features_ms"] + row["denoise_ms"]
             rows.append(row)
             print(json.dumps(row), flush=True)
+            if args.variance_filter:            # the same input through the pre-filter
+                runs = [timed(lambda: rtnw.denoise(color, f, mom, spp, variance_filter=1, timing=True))
+                        for _ in range(args.rounds + 1)][1:]
+                row = dict(row, variance_filter=1, denoise_ms=statistics.median(ms for ms, _ in runs),
+                           denoise_kernel_ms=statistics.median(k for _, (_, k) in runs),
+                           rms_denoised=gamma_rms(runs[-1][1][0], ref))
+                row["total_denoised_ms"] = row["render_ms"] + row["features_ms"] + row["denoise_ms"]
+                rows.append(row)
+                print(json.dumps(row), flush=True)
         if args.sweep:
             for it in (3, 4, 5, 6):
                 for sc in (1.0, 2.0, 4.0, 8.0, 16.0):
@@ -181,10 +196,11 @@ def main():
         json.dump({"tool": "tools/denoise_probe.py", "args": vars(args), "rows": rows, "sweep": sweep, "timing": timing},
                   f, indent=1)
     with open(os.path.join(args.out, "denoise_probe.md"), "w") as f:
-        f.write("| config | input | samples (share of cap) | render ms | features ms | denoise ms (kernels) | total raw ms | "
-                "total denoised ms | gamma RMS raw | gamma RMS denoised |\n|---|---|---|---|---|---|---|---|---|---|\n")
+        f.write("| config | input | variance filter | samples (share of cap) | render ms | features ms | denoise ms (kernels) | total raw ms | "
+                "total denoised ms | gamma RMS raw | gamma RMS denoised |\n|---|---|---|---|---|---|---|---|---|---|---|\n")
         for r in rows:
-            f.write(f"| {r['config']} {r['scene']} {r['nx']}x{r['ny']} cap {r['cap']} | {r['input']} | "
+            f.write(f"| {r['config']} {r['scene']} {r['nx']}x{r['ny']} cap {r['cap']} | {r['input']}"
+                    f"{'' if r['guard_radius'] is None else ' guard ' + str(r['guard_radius'])} | {r['variance_filter']} | "
                     f"{r['samples']:.0f} ({r['samples_share']:.3f}) | {r['render_ms']:.2f} | {r['features_ms']:.2f} | "
                     f"{r['denoise_ms']:.2f} ({r['denoise_kernel_ms']:.3f}) | {r['total_raw_ms']:.2f} | "
                     f"{r['total_denoised_ms']:.2f} | {r['rms_raw']:.5f} | {r['rms_denoised']:.5f} |\n")
