@@ -107,7 +107,8 @@ typedef struct rt_image {    /* texels of one image_texture (surface_texture.h:1
 
 typedef struct rt_medium {   /* constant_medium.h:14-50 */
     int32_t boundary_first;  /* range in rt_scene_desc.boundary_prims */
-    int32_t boundary_count;
+    int32_t boundary_count;  /* >= 1: a medium needs at least one boundary primitive
+                                (rt_scene_create returns RT_ERR_UNSUPPORTED for 0) */
     float density;
     int32_t material;        /* the isotropic phase material */
     int32_t order;           /* number of surface prims before it in list order */

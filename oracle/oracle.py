@@ -22,6 +22,7 @@ SCENES = {
     "random_scene": 0, "random_motion": 1, "cornell_box": 2, "cornell_smoke": 3,
     "final": 4, "simple_light": 5, "two_spheres": 6, "test": 7, "earth": 8,
     "edge_empty": 9, "edge_single": 10, "edge_degenerate": 11,   # the tests' edge cases (ref_harness.cpp edge_*)
+    "edge_chains": 12,
 }
 EARTH_PNG = os.path.join(os.path.dirname(HERE), "tests", "golden", "picture.png")   # main.cpp:93's asset
 CAMERAS = {"cornell": 0, "random": 1, "final_alt": 2}
@@ -40,6 +41,7 @@ SCENE_DEFAULTS = {
     "edge_empty": dict(camera="random", background="sky", max_depth=50),
     "edge_single": dict(camera="random", background="sky", max_depth=50),
     "edge_degenerate": dict(camera="random", background="sky", max_depth=50),
+    "edge_chains": dict(camera="random", background="sky", max_depth=50),
 }
 
 
@@ -163,6 +165,12 @@ def lib():
         L.oracle_scene_dump.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_long]
         L.oracle_set_image.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.oracle_scene_dump.restype = ctypes.c_long
+        L.oracle_render_desc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(OracleParams), ctypes.c_void_p,
+                                         ctypes.POINTER(OracleStats)]
+        L.oracle_render_desc.restype = ctypes.c_int
+        L.oracle_first_hits_desc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(OracleParams)] + \
+            [ctypes.c_void_p] * 4
+        L.oracle_first_hits_desc.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -216,6 +224,80 @@ def kernel_spec(scene: str, nx: int, ny: int, ns: int, *, seed: int = 0, chunk: 
     media after surfaces, forward throughput, chunked partial sums)."""
     return RenderSpec(scene=scene, nx=nx, ny=ny, ns=ns, rng="counter", seed=seed, media_after=True,
                       forward=True, chunk=chunk, **kw)
+
+
+def _desc_params(spec: RenderSpec):
+    """oracle_params of a descriptor render: spec.scene and spec.camera are not used, the depth
+    and background must be given."""
+    if spec.max_depth is None or spec.background is None:
+        raise ValueError("a descriptor render needs max_depth and background")
+    if spec.rng != "counter":
+        raise ValueError("a descriptor render uses the counter RNG")
+    x0, y0, w, h = spec.rect if spec.rect else (0, 0, spec.nx, spec.ny)
+    p = OracleParams(scene=-1, nx=spec.nx, ny=spec.ny, ns=spec.ns, max_depth=spec.max_depth,
+                     background=1 if spec.background == "sky" else 0, tmin=spec.tmin, camera=0, rng=1,
+                     media_after=int(spec.media_after), forward=int(spec.forward), chunk=spec.chunk,
+                     x0=x0, y0=y0, w=w, h=h, threads=spec.threads, sample_offset=spec.sample_offset, seed=spec.seed)
+    return p, w, h
+
+
+def _desc_pointers(desc, cam):
+    """Addresses of an rtnw.SceneDesc's rt_scene_desc and an rtnw.Camera's rt_camera_desc."""
+    return ctypes.cast(desc.ptr, ctypes.c_void_p), ctypes.cast(ctypes.pointer(cam.desc), ctypes.c_void_p)
+
+
+def desc_spec(nx: int, ny: int, ns: int, *, max_depth: int, background: str, seed: int = 0, chunk: int = 0,
+              forward: bool = True, media_after: bool = True, **kw) -> RenderSpec:
+    """The spec of a descriptor render: kernel_spec's statement by default (forward=False is
+    the right-fold mode RT_FLAG_RIGHT_FOLD implements)."""
+    return RenderSpec(scene="", nx=nx, ny=ny, ns=ns, rng="counter", seed=seed, media_after=media_after,
+                      forward=forward, chunk=chunk, max_depth=max_depth, background=background, **kw)
+
+
+def render_desc(desc, cam, spec: RenderSpec):
+    """oracle_render_desc: the oracle's image of any rtnw.SceneDesc through an rtnw.Camera.
+    Returns (mean float32 array [h, w, 3], stats dict)."""
+    p, w, h = _desc_params(spec)
+    dp, cp = _desc_pointers(desc, cam)
+    out = np.zeros((h, w, 3), dtype=np.float32)
+    st = OracleStats()
+    rc = lib().oracle_render_desc(dp, cp, ctypes.byref(p), out.ctypes.data, ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"oracle_render_desc failed: {rc}")
+    return out, {"samples": st.samples, "segments": st.segments, "seconds": st.seconds}
+
+
+def first_hits_desc(desc, cam, spec: RenderSpec):
+    """oracle_first_hits_desc: per camera sample the first surface hit, media skipped.  A dict
+    of prim [h, w, ns] int32 (-1: miss), hit [h, w, ns] bool, depth [h, w, ns], normal and
+    albedo [h, w, ns, 3], float32."""
+    p, w, h = _desc_params(spec)
+    dp, cp = _desc_pointers(desc, cam)
+    prim = np.zeros((h, w, spec.ns), np.int32)
+    depth = np.zeros((h, w, spec.ns), np.float32)
+    normal = np.zeros((h, w, spec.ns, 3), np.float32)
+    albedo = np.zeros((h, w, spec.ns, 3), np.float32)
+    rc = lib().oracle_first_hits_desc(dp, cp, ctypes.byref(p), prim.ctypes.data, depth.ctypes.data, normal.ctypes.data,
+                                      albedo.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_first_hits_desc failed: {rc}")
+    return dict(prim=prim, hit=prim >= 0, depth=depth, normal=normal, albedo=albedo)
+
+
+def feature_means(fh):
+    """What rt_render_features writes for those samples: each buffer's samples added in sample
+    order in float32, the sum times float(1.0 / spp).  albedo, normal [h, w, 3]; depth,
+    coverage [h, w]."""
+    ns = fh["prim"].shape[-1]
+    k = np.float32(1.0 / ns)
+
+    def mean(a):   # [h, w, ns, ...] -> [h, w, ...]
+        acc = np.zeros(a.shape[:2] + a.shape[3:], np.float32)
+        for s in range(ns):
+            acc = acc + a[:, :, s]
+        return acc * k
+    return dict(albedo=mean(fh["albedo"]), normal=mean(fh["normal"]), depth=mean(fh["depth"]),
+                coverage=mean(fh["hit"].astype(np.float32)))
 
 
 def quantize(mean: np.ndarray) -> np.ndarray:

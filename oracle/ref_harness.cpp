@@ -308,6 +308,35 @@ static hitable *edge_degenerate() {
     l[i++] = new flip_normals(new xy_rect(-3, 3, 0, 3, -3, new diffuse_light(new constant_texture(vec3(2, 2, 2)))));
     return new hitable_list(l, i);
 }
+static hitable *edge_chains() {   // instance chains, nested checkers, specular rects, a medium in a translated sphere
+    hitable **l = new hitable *[12];
+    int i = 0;
+    texture *noise = new noise_texture(2);
+    texture *nested = new checker_texture(new checker_texture(new constant_texture(vec3(0.9, 0.1, 0.1)), noise),
+                                          new checker_texture(noise, new constant_texture(vec3(0.1, 0.1, 0.9))));
+    material *white = new lambertian(new constant_texture(vec3(0.73, 0.73, 0.73)));
+    material *glass = new dielectric(1.5);
+    l[i++] = new xz_rect(-6, 6, -6, 6, 0, new lambertian(nested));                       // checker of checkers over noise
+    l[i++] = new translate(new rotate_y(new sphere(vec3(0, 0, 0), 0.6, white), 30), vec3(-2, 0.6, 0));
+    l[i++] = new translate(new rotate_y(new moving_sphere(vec3(0, 0, 0), vec3(0.3, 0.2, 0), 0, 1, 0.5,
+                                                          new lambertian(new constant_texture(vec3(0.2, 0.8, 0.2)))), -20),
+                           vec3(2, 0.5, 0.5));
+    l[i++] = new translate(new flip_normals(new rotate_y(new xy_rect(-0.8, 0.8, 0, 1.2, 0,   // a flip between two transforms
+                                                                     new lambertian(new constant_texture(vec3(0.8, 0.3, 0.3)))), 25)),
+                           vec3(0, 0, -2));
+    l[i++] = new translate(new rotate_y(new translate(new flip_normals(new rotate_y(new translate(   // a chain of 6
+                 new sphere(vec3(0, 0, 0), 0.4, new lambertian(noise)), vec3(0.2, 0, 0)), 40)), vec3(0, 0.1, 0.3)), -15),
+                           vec3(-0.5, 0.4, 1.2));
+    l[i++] = new xz_rect(-1.8, -0.6, 1.8, 3, 0.3, new metal(vec3(0.8, 0.8, 0.9), 0.0));
+    l[i++] = new xz_rect(0.6, 1.8, 1.8, 3, 0.3, glass);
+    l[i++] = new constant_medium(new translate(new sphere(vec3(0, 0, 0), 0.7, glass), vec3(0.8, 0.8, -0.5)), 1.5,
+                                 new constant_texture(vec3(0.9, 0.9, 0.9)));
+    l[i++] = new translate(new rotate_y(new box(vec3(0, 0, 0), vec3(0.7, 0.9, 0.7), white), -18), vec3(3, 0, -1.5));
+    l[i++] = new sphere(vec3(3.2, 0.45, 1.6), 0.45, glass);
+    l[i++] = new moving_sphere(vec3(-3.2, 0.4, 1.5), vec3(-3.2, 0.7, 1.5), 0, 1, 0.4, new metal(vec3(0.9, 0.7, 0.5), 0.2));
+    l[i++] = new xz_rect(-1, 1, -1, 1, 4, new diffuse_light(new constant_texture(vec3(6, 6, 6))));
+    return new hitable_list(l, i);
+}
 
 // ----------------------------------------------------------------------- CLI
 static void usage() {
@@ -316,7 +345,7 @@ static void usage() {
         "           [--cam cornell|random|final_alt] [--rng canonical|counter --seed S]\n"
         "           [--rows J0:J1] [--ppm FILE] [--fb FILE] [--dump FILE] [--perlin FILE] [--time] [--accel flat|bvh]\n"
         "  scenes: random_scene random_motion cornell_box cornell_smoke final simple_light two_spheres test\n"
-        "          edge_empty edge_single edge_degenerate (sky, random camera)\n");
+        "          edge_empty edge_single edge_degenerate edge_chains (sky, random camera)\n");
     exit(2);
 }
 
@@ -374,6 +403,7 @@ int main(int argc, char **argv) {
     else if (scene == "edge_empty") { world = edge_empty(); sky_default = true; cam_default = "random"; }
     else if (scene == "edge_single") { world = edge_single(); sky_default = true; cam_default = "random"; }
     else if (scene == "edge_degenerate") { world = edge_degenerate(); sky_default = true; cam_default = "random"; }
+    else if (scene == "edge_chains") { world = edge_chains(); sky_default = true; cam_default = "random"; }
     else if (scene == "earth") {   // stbi_load("picture.png") reads the working directory (main.cpp:93)
         if (!assets.empty() && chdir(assets.c_str()) != 0) { perror("chdir"); return 2; }
         world = earth();

@@ -108,18 +108,20 @@ static inline double rng_medium(rng_t *g, int bounce, int k) {
 }
 
 /* ---------------------------------------------------------------- Perlin */
-static v3 g_ranvec[256];
-static int g_perm[3][256];
+/* The tables of one scene.  The built-in scenes share g_perlin (the reference's statics, the
+ * same values in every process); a descriptor's scene carries its own copy (scene_from_desc). */
+typedef struct { v3 ranvec[256]; int perm[3][256]; } perlin_t;
+static perlin_t g_perlin;
 
 static void perlin_generate(rng_t *g) {                                  /* perlin.h:82-111 */
     for (int i = 0; i < 256; ++i) {
         double x = -1 + 2 * rng_next(g);
         double y = -1 + 2 * rng_next(g);
         double z = -1 + 2 * rng_next(g);
-        g_ranvec[i] = vunit(V((float)x, (float)y, (float)z));
+        g_perlin.ranvec[i] = vunit(V((float)x, (float)y, (float)z));
     }
     for (int a = 0; a < 3; a++) {
-        int *p = g_perm[a];
+        int *p = g_perlin.perm[a];
         for (int i = 0; i < 256; i++) p[i] = i;
         for (int i = 255; i > 0; i--) {                                  /* permute, perlin.h:90-97 */
             int target = (int)(rng_next(g) * (i + 1));
@@ -128,7 +130,7 @@ static void perlin_generate(rng_t *g) {                                  /* perl
     }
 }
 
-static float perlin_noise(v3 p) {                                        /* perlin.h:43-61 */
+static float perlin_noise(const perlin_t *pl, v3 p) {                                        /* perlin.h:43-61 */
     float u = p.e[0] - floorf(p.e[0]);
     float v = p.e[1] - floorf(p.e[1]);
     float w = p.e[2] - floorf(p.e[2]);
@@ -142,7 +144,7 @@ static float perlin_noise(v3 p) {                                        /* perl
     for (int di = 0; di < 2; di++)
         for (int dj = 0; dj < 2; dj++)
             for (int dk = 0; dk < 2; dk++)
-                c[di][dj][dk] = g_ranvec[g_perm[0][(i + di) & 255] ^ g_perm[1][(j + dj) & 255] ^ g_perm[2][(k + dk) & 255]];
+                c[di][dj][dk] = pl->ranvec[pl->perm[0][(i + di) & 255] ^ pl->perm[1][(j + dj) & 255] ^ pl->perm[2][(k + dk) & 255]];
     /* perlin_interp, perlin.h:25-39 (the Hermite smoothing is applied again) */
     float uu = u * u * (3 - 2 * u);
     float vv = v * v * (3 - 2 * v);
@@ -158,12 +160,12 @@ static float perlin_noise(v3 p) {                                        /* perl
     return accum;
 }
 
-static float perlin_turb(v3 p) {                                         /* perlin.h:64-74 */
+static float perlin_turb(const perlin_t *pl, v3 p) {                                         /* perlin.h:64-74 */
     float accum = 0;
     v3 temp_p = p;
     float weight = 1.0;
     for (int i = 0; i < 7; i++) {
-        accum += weight * perlin_noise(temp_p);
+        accum += weight * perlin_noise(pl, temp_p);
         weight = (float)(weight * 0.5);
         temp_p = V(temp_p.e[0] * 2, temp_p.e[1] * 2, temp_p.e[2] * 2);
     }
@@ -175,6 +177,7 @@ enum { TX_CONST, TX_CHECKER, TX_NOISE, TX_IMAGE };
 typedef struct tex_s {
     int kind; v3 color; const struct tex_s *even, *odd; float scale;
     const unsigned char *data; int nx, ny;   /* image_texture, surface_texture.h:13-16 */
+    const perlin_t *pl;                      /* noise_texture: the scene's tables */
 } tex_t;
 
 static v3 tex_value(const tex_t *t, float u, float v, v3 p) {
@@ -198,7 +201,7 @@ static v3 tex_value(const tex_t *t, float u, float v, v3 p) {
             return V(r, g, b);
         }
         /* noise_texture, texture.h:52-56 */
-        float s = 1 + sinf(t->scale * p.e[0] + 5 * perlin_turb(vscale(t->scale, p)));
+        float s = 1 + sinf(t->scale * p.e[0] + 5 * perlin_turb(t->pl, vscale(t->scale, p)));
         v3 half = V(0.5f * 1, 0.5f * 1, 0.5f * 1);
         return V(s * half.e[0], s * half.e[1], s * half.e[2]);
     }
@@ -208,7 +211,7 @@ static v3 tex_value(const tex_t *t, float u, float v, v3 p) {
 enum { MT_LAMBERT, MT_METAL, MT_DIELECTRIC, MT_LIGHT, MT_ISOTROPIC };
 typedef struct mat_s { int kind; const tex_t *tex; v3 albedo; float fuzz; float ri; } mat_t;
 
-typedef struct { float t, u, v; v3 p, normal; const mat_t *mat; } hit_t;   /* hitable.h:21-29 */
+typedef struct { float t, u, v; v3 p, normal; const mat_t *mat; int prim; } hit_t;   /* hitable.h:21-29 */
 
 static v3 random_in_unit_sphere(rng_t *g) {                               /* material.h:41-47 */
     v3 p;
@@ -302,6 +305,7 @@ typedef struct obj_s {
     struct obj_s *child;                 /* flip / translate / rotate / medium boundary */
     v3 offset; float sin_t, cos_t;       /* translate / rotate_y */
     float density; int ordinal;          /* medium */
+    int id;                              /* leaves of a descriptor: index in rt_scene_desc.prims */
 } obj_t;
 
 typedef struct {
@@ -340,6 +344,7 @@ static int medium_hit(const obj_t *o, const ray_t *r, float t_min, float t_max, 
                 rec->p = ray_at(r, rec->t);
                 rec->normal = V(1, 0, 0);
                 rec->mat = o->mat;
+                rec->prim = o->id;
                 return 1;
             }
         }
@@ -378,6 +383,7 @@ static int obj_hit(const obj_t *o, const ray_t *r, float tmin, float tmax, hit_t
                 sphere_uv(vdivs(vsub(rec->p, o->c0), o->r), &rec->u, &rec->v);
                 rec->normal = vdivs(vsub(rec->p, o->c0), o->r);
                 rec->mat = o->mat;
+                rec->prim = o->id;
                 return 1;
             }
         }
@@ -397,6 +403,7 @@ static int obj_hit(const obj_t *o, const ray_t *r, float tmin, float tmax, hit_t
                 rec->p = ray_at(r, rec->t);
                 rec->normal = vdivs(vsub(rec->p, msphere_center(o, r->time)), o->r);
                 rec->mat = o->mat;
+                rec->prim = o->id;
                 return 1;
             }
         }
@@ -415,6 +422,7 @@ static int obj_hit(const obj_t *o, const ray_t *r, float tmin, float tmax, hit_t
         rec->v = (b - o->b0) / (o->b1 - o->b0);
         rec->t = t;
         rec->mat = o->mat;
+        rec->prim = o->id;
         rec->p = ray_at(r, t);
         rec->normal = V(ax == 0, ax == 1, ax == 2);
         return 1;
@@ -460,7 +468,7 @@ static int obj_hit(const obj_t *o, const ray_t *r, float tmin, float tmax, hit_t
 typedef struct {
     void **blocks; int nblocks, cap;
     obj_t *world;
-    obj_t *media[64]; int nmedia;
+    obj_t **media; int nmedia, media_cap;
 } scene_t;
 
 static void *arena_alloc(scene_t *s, size_t n) {
@@ -472,6 +480,7 @@ static void *arena_alloc(scene_t *s, size_t n) {
 static void scene_free(scene_t *s) {
     for (int i = 0; i < s->nblocks; i++) free(s->blocks[i]);
     free(s->blocks);
+    free(s->media);
 }
 
 static tex_t *t_const(scene_t *s, double r, double g, double b) {
@@ -481,7 +490,7 @@ static tex_t *t_checker(scene_t *s, const tex_t *even, const tex_t *odd) {
     tex_t *t = arena_alloc(s, sizeof *t); t->kind = TX_CHECKER; t->even = even; t->odd = odd; return t;
 }
 static tex_t *t_noise(scene_t *s, double scale) {
-    tex_t *t = arena_alloc(s, sizeof *t); t->kind = TX_NOISE; t->scale = (float)scale; return t;
+    tex_t *t = arena_alloc(s, sizeof *t); t->kind = TX_NOISE; t->scale = (float)scale; t->pl = &g_perlin; return t;
 }
 static mat_t *m_lambert(scene_t *s, const tex_t *t) { mat_t *m = arena_alloc(s, sizeof *m); m->kind = MT_LAMBERT; m->tex = t; return m; }
 static mat_t *m_light(scene_t *s, const tex_t *t) { mat_t *m = arena_alloc(s, sizeof *m); m->kind = MT_LIGHT; m->tex = t; return m; }
@@ -703,11 +712,48 @@ static obj_t *build_edge_degenerate(scene_t *s) {
     return o_list(s, list, i);
 }
 
+static obj_t *build_edge_chains(scene_t *s) {
+    obj_t **list = o_array(s, 12);
+    int i = 0;
+    tex_t *noise = t_noise(s, 2);
+    tex_t *nested = t_checker(s, t_checker(s, t_const(s, 0.9, 0.1, 0.1), noise), t_checker(s, noise, t_const(s, 0.1, 0.1, 0.9)));
+    mat_t *white = m_lambert(s, t_const(s, 0.73, 0.73, 0.73));
+    mat_t *glass = m_dielectric(s, 1.5);
+    list[i++] = o_rect(s, OB_XZ, -6, 6, -6, 6, 0, m_lambert(s, nested));
+    list[i++] = o_translate(s, o_rotate_y(s, o_sphere(s, V(0, 0, 0), 0.6f, white), 30), V(-2, 0.6f, 0));
+    list[i++] = o_translate(s, o_rotate_y(s, o_msphere(s, V(0, 0, 0), V(0.3f, 0.2f, 0), 0, 1, 0.5f,
+                                                       m_lambert(s, t_const(s, 0.2, 0.8, 0.2))), -20), V(2, 0.5f, 0.5f));
+    list[i++] = o_translate(s, o_flip(s, o_rotate_y(s, o_rect(s, OB_XY, -0.8f, 0.8f, 0, 1.2f, 0,
+                                                              m_lambert(s, t_const(s, 0.8, 0.3, 0.3))), 25)), V(0, 0, -2));
+    list[i++] = o_translate(s, o_rotate_y(s, o_translate(s, o_flip(s, o_rotate_y(s, o_translate(s,
+                    o_sphere(s, V(0, 0, 0), 0.4f, m_lambert(s, noise)), V(0.2f, 0, 0)), 40)), V(0, 0.1f, 0.3f)), -15),
+                            V(-0.5f, 0.4f, 1.2f));
+    list[i++] = o_rect(s, OB_XZ, -1.8f, -0.6f, 1.8f, 3, 0.3f, m_metal(s, V(0.8f, 0.8f, 0.9f), 0.0f));
+    list[i++] = o_rect(s, OB_XZ, 0.6f, 1.8f, 1.8f, 3, 0.3f, glass);
+    list[i++] = o_medium(s, o_translate(s, o_sphere(s, V(0, 0, 0), 0.7f, glass), V(0.8f, 0.8f, -0.5f)), 1.5f, t_const(s, 0.9, 0.9, 0.9));
+    list[i++] = o_translate(s, o_rotate_y(s, o_box(s, V(0, 0, 0), V(0.7f, 0.9f, 0.7f), white), -18), V(3, 0, -1.5f));
+    list[i++] = o_sphere(s, V(3.2f, 0.45f, 1.6f), 0.45f, glass);
+    list[i++] = o_msphere(s, V(-3.2f, 0.4f, 1.5f), V(-3.2f, 0.7f, 1.5f), 0, 1, 0.4f, m_metal(s, V(0.9f, 0.7f, 0.5f), 0.2f));
+    list[i++] = o_rect(s, OB_XZ, -1, 1, -1, 1, 4, m_light(s, t_const(s, 6, 6, 6)));
+    return o_list(s, list, i);
+}
+
+static void scene_add_medium(scene_t *s, obj_t *o) {
+    if (s->nmedia == s->media_cap) {
+        int cap = s->media_cap ? 2 * s->media_cap : 16;
+        obj_t **m = realloc(s->media, (size_t)cap * sizeof(obj_t *));
+        if (!m) { fprintf(stderr, "rt_oracle: out of memory (media list)\n"); abort(); }   /* as a failed arena block would end */
+        s->media = m;
+        s->media_cap = cap;
+    }
+    s->media[s->nmedia++] = o;
+}
+
 static void collect_media(scene_t *s, obj_t *o) {
     switch (o->kind) {
     case OB_LIST: for (int i = 0; i < o->nkids; i++) collect_media(s, o->kids[i]); break;
     case OB_BOX: case OB_FLIP: case OB_TRANSLATE: case OB_ROTY: collect_media(s, o->child); break;
-    case OB_MEDIUM: o->ordinal = s->nmedia; s->media[s->nmedia++] = o; break;
+    case OB_MEDIUM: o->ordinal = s->nmedia; scene_add_medium(s, o); break;
     default: break;
     }
 }
@@ -731,6 +777,7 @@ static int scene_build(scene_t *s, int which, rng_t *g_after) {
     case ORACLE_SCENE_EDGE_EMPTY: s->world = build_edge_empty(s); break;
     case ORACLE_SCENE_EDGE_SINGLE: s->world = build_edge_single(s); break;
     case ORACLE_SCENE_EDGE_DEGENERATE: s->world = build_edge_degenerate(s); break;
+    case ORACLE_SCENE_EDGE_CHAINS: s->world = build_edge_chains(s); break;
     default: return -1;
     }
     collect_media(s, s->world);
@@ -875,21 +922,22 @@ static v3 render_pixel(run_t *rn, const cam_t *cam, int i, int j, rng_t *g) {
     return V(col.e[0] * k, col.e[1] * k, col.e[2] * k);
 }
 
-int oracle_render(const oracle_params *p, float *out, oracle_stats *stats) {
-    scene_t sc;
-    if (p->nx <= 0 || p->ny <= 0 || p->ns <= 0) return -1;
-    rng_t g_canon;
-    if (scene_build(&sc, p->scene, &g_canon) != 0) return -2;
+/* The pixel loops over a built scene: oracle_render (a built-in scene, a preset camera) and
+ * oracle_render_desc (both as given) share them. */
+static int render_scene(const scene_t *scp, const cam_t *camp, const rng_t *g_canon_p, const oracle_params *p, float *out,
+                        oracle_stats *stats) {
+    const scene_t sc = *scp;
+    const cam_t cam = *camp;
     int x0 = p->x0, y0 = p->y0, w = p->w, h = p->h;
     if (w <= 0) { x0 = 0; y0 = 0; w = p->nx; h = p->ny; }
-    if (x0 < 0 || y0 < 0 || x0 + w > p->nx || y0 + h > p->ny) { scene_free(&sc); return -3; }
-    cam_t cam = camera_preset(p->camera, p->nx, p->ny);
+    if (x0 < 0 || y0 < 0 || x0 + w > p->nx || y0 + h > p->ny) return -3;
+    if (p->rng == 0 && !g_canon_p) return -4;
     struct timespec ta, tb;
     clock_gettime(CLOCK_MONOTONIC, &ta);
     double segments = 0;
     if (p->rng == 0) {
         /* canonical stream: the whole image in reference order (main.cpp:299-304) */
-        rng_t g = g_canon;
+        rng_t g = *g_canon_p;
         run_t rn = { &sc, p, 0 };
         for (int j = p->ny - 1; j >= 0; j--) {
             for (int i = 0; i < p->nx; i++) {
@@ -924,6 +972,217 @@ int oracle_render(const oracle_params *p, float *out, oracle_stats *stats) {
         stats->segments = segments;
         stats->seconds = (tb.tv_sec - ta.tv_sec) + 1e-9 * (tb.tv_nsec - ta.tv_nsec);
     }
+    return 0;
+}
+
+int oracle_render(const oracle_params *p, float *out, oracle_stats *stats) {
+    scene_t sc;
+    if (p->nx <= 0 || p->ny <= 0 || p->ns <= 0) return -1;
+    rng_t g_canon;
+    if (scene_build(&sc, p->scene, &g_canon) != 0) return -2;
+    cam_t cam = camera_preset(p->camera, p->nx, p->ny);
+    int rc = render_scene(&sc, &cam, &g_canon, p, out, stats);
+    scene_free(&sc);
+    return rc;
+}
+
+/* ------------------------------------------------ scenes from a descriptor
+ * The object tree of an rt_scene_desc (include/rt_hip.h), as the host API would have built
+ * it before flattening: every primitive a leaf (under a flip_normals if `flip`), wrapped in
+ * its instance chain from the innermost (last) op to ops[0] outermost; the world one
+ * hitable_list in list order with each constant_medium at its `order` position over a
+ * hitable_list of its boundary primitives.  Textures, materials, images and the Perlin
+ * tables are the descriptor's; nothing here is process-wide. */
+static obj_t *desc_prim(scene_t *s, const rt_scene_desc *d, const rt_prim *pr, int id, const mat_t *mats) {
+    const float *p = pr->p;
+    const mat_t *m = &mats[pr->material];
+    obj_t *o;
+    switch (pr->kind) {
+    case RT_PRIM_SPHERE: o = o_sphere(s, V(p[0], p[1], p[2]), p[3], m); break;
+    case RT_PRIM_MOVING_SPHERE: o = o_msphere(s, V(p[0], p[1], p[2]), V(p[3], p[4], p[5]), p[6], p[7], p[8], m); break;
+    case RT_PRIM_XY_RECT: o = o_rect(s, OB_XY, p[0], p[1], p[2], p[3], p[4], m); break;
+    case RT_PRIM_XZ_RECT: o = o_rect(s, OB_XZ, p[0], p[1], p[2], p[3], p[4], m); break;
+    default: o = o_rect(s, OB_YZ, p[0], p[1], p[2], p[3], p[4], m); break;
+    }
+    o->id = id;
+    if (pr->flip) o = o_flip(s, o);
+    if (pr->instance >= 0) {
+        const rt_instance *in = &d->instances[pr->instance];
+        for (int k = in->nops - 1; k >= 0; k--) {
+            const float *op = in->ops[k];
+            if ((int)op[0] == RT_OP_TRANSLATE) o = o_translate(s, o, V(op[1], op[2], op[3]));
+            else if ((int)op[0] == RT_OP_ROTATE_Y) {
+                obj_t *r = o_new(s, OB_ROTY);
+                r->child = o; r->sin_t = op[1]; r->cos_t = op[2];
+                o = r;
+            } else o = o_flip(s, o);
+        }
+    }
+    return o;
+}
+
+static int desc_prim_ok(const rt_scene_desc *d, const rt_prim *pr) {
+    if (pr->kind < RT_PRIM_SPHERE || pr->kind > RT_PRIM_YZ_RECT) return 0;
+    if (pr->material < 0 || pr->material >= d->nmaterials) return 0;
+    if (pr->instance < -1 || pr->instance >= d->ninstances) return 0;
+    if (pr->instance >= 0) {
+        const rt_instance *in = &d->instances[pr->instance];
+        if (in->nops < 0 || in->nops > 6) return 0;
+        for (int k = 0; k < in->nops; k++) if ((int)in->ops[k][0] < RT_OP_TRANSLATE || (int)in->ops[k][0] > RT_OP_FLIP) return 0;
+    }
+    return 1;
+}
+
+static int scene_from_desc(scene_t *s, const rt_scene_desc *d) {
+    memset(s, 0, sizeof *s);
+    if (!d || d->abi_version != RT_ABI_VERSION) return -1;
+    if (d->nprims < 0 || d->nboundary < 0 || d->nmedia < 0 || d->nmaterials < 0 || d->ntextures < 0 || d->ninstances < 0 ||
+        d->nimages < 0)
+        return -1;
+    if (!d->perlin_ranvec || !d->perlin_perm) return -1;   /* as rt_scene_create: "missing Perlin tables" */
+    for (int i = 0; i < 768; i++) if (d->perlin_perm[i] < 0 || d->perlin_perm[i] > 255) return -1;
+    /* media stand in list order: `order` must not decrease, or the tree would not be the one the fields state */
+    for (int i = 1; i < d->nmedia; i++) if (d->media[i].order < d->media[i - 1].order) return -1;
+    perlin_t *pl = arena_alloc(s, sizeof *pl);
+    for (int i = 0; i < 256; i++) pl->ranvec[i] = V(d->perlin_ranvec[3 * i], d->perlin_ranvec[3 * i + 1], d->perlin_ranvec[3 * i + 2]);
+    for (int a = 0; a < 3; a++) for (int i = 0; i < 256; i++) pl->perm[a][i] = d->perlin_perm[256 * a + i];
+    tex_t *tex = arena_alloc(s, sizeof(tex_t) * (size_t)(d->ntextures + 1));
+    for (int i = 0; i < d->ntextures; i++) {
+        const rt_texture *t = &d->textures[i];
+        tex_t *o = &tex[i];
+        switch (t->kind) {
+        case RT_TEX_CONSTANT: o->kind = TX_CONST; o->color = V(t->color[0], t->color[1], t->color[2]); break;
+        case RT_TEX_CHECKER:
+            if (t->even < 0 || t->even >= d->ntextures || t->odd < 0 || t->odd >= d->ntextures) return -1;
+            o->kind = TX_CHECKER; o->even = &tex[t->even]; o->odd = &tex[t->odd]; break;
+        case RT_TEX_NOISE: o->kind = TX_NOISE; o->scale = t->scale; o->pl = pl; break;
+        case RT_TEX_IMAGE: {
+            if (t->image < 0 || t->image >= d->nimages) return -1;
+            const rt_image *im = &d->images[t->image];
+            if (im->nx <= 0 || im->ny <= 0 || im->offset < 0 || im->offset + (int64_t)3 * im->nx * im->ny > d->image_bytes) return -1;
+            o->kind = TX_IMAGE; o->data = d->image_data + im->offset; o->nx = im->nx; o->ny = im->ny; break;
+        }
+        default: return -1;
+        }
+    }
+    mat_t *mats = arena_alloc(s, sizeof(mat_t) * (size_t)(d->nmaterials + 1));
+    for (int i = 0; i < d->nmaterials; i++) {
+        const rt_material *m = &d->materials[i];
+        mat_t *o = &mats[i];
+        switch (m->kind) {
+        case RT_MAT_LAMBERTIAN: o->kind = MT_LAMBERT; break;
+        case RT_MAT_METAL: o->kind = MT_METAL; break;
+        case RT_MAT_DIELECTRIC: o->kind = MT_DIELECTRIC; break;
+        case RT_MAT_DIFFUSE_LIGHT: o->kind = MT_LIGHT; break;
+        case RT_MAT_ISOTROPIC: o->kind = MT_ISOTROPIC; break;
+        default: return -1;
+        }
+        if (o->kind == MT_LAMBERT || o->kind == MT_LIGHT || o->kind == MT_ISOTROPIC) {
+            if (m->texture < 0 || m->texture >= d->ntextures) return -1;
+            o->tex = &tex[m->texture];
+        }
+        o->albedo = V(m->albedo[0], m->albedo[1], m->albedo[2]);
+        o->fuzz = m->fuzz;      /* clamped by the host (material.h:76) */
+        o->ri = m->ref_idx;
+    }
+    for (int i = 0; i < d->nprims; i++) if (!desc_prim_ok(d, &d->prims[i])) return -1;
+    for (int i = 0; i < d->nboundary; i++) if (!desc_prim_ok(d, &d->boundary_prims[i])) return -1;
+    obj_t **list = o_array(s, d->nprims + d->nmedia + 1);
+    int n = 0, mi = 0;
+    for (int q = 0; q <= d->nprims; q++) {
+        /* media are listed in list order: those with `order` surface primitives before them */
+        while (mi < d->nmedia && (d->media[mi].order <= q || q == d->nprims)) {
+            const rt_medium *m = &d->media[mi];
+            if (m->boundary_first < 0 || m->boundary_count < 0 || m->boundary_first + m->boundary_count > d->nboundary) return -1;
+            if (m->material < 0 || m->material >= d->nmaterials) return -1;
+            obj_t **b = o_array(s, m->boundary_count + 1);
+            for (int k = 0; k < m->boundary_count; k++)
+                b[k] = desc_prim(s, d, &d->boundary_prims[m->boundary_first + k], m->boundary_first + k, mats);
+            obj_t *o = o_new(s, OB_MEDIUM);
+            o->child = o_list(s, b, m->boundary_count);
+            o->density = m->density;
+            o->mat = &mats[m->material];
+            o->ordinal = mi++;
+            scene_add_medium(s, o);
+            list[n++] = o;
+        }
+        if (q < d->nprims) list[n++] = desc_prim(s, d, &d->prims[q], q, mats);
+    }
+    s->world = o_list(s, list, n);
+    return 0;
+}
+
+static cam_t camera_from_desc(const rt_camera_desc *c) {
+    cam_t o;
+    o.origin = V(c->origin[0], c->origin[1], c->origin[2]);
+    o.llc = V(c->lower_left_corner[0], c->lower_left_corner[1], c->lower_left_corner[2]);
+    o.horizontal = V(c->horizontal[0], c->horizontal[1], c->horizontal[2]);
+    o.vertical = V(c->vertical[0], c->vertical[1], c->vertical[2]);
+    o.u = V(c->u[0], c->u[1], c->u[2]);
+    o.v = V(c->v[0], c->v[1], c->v[2]);
+    o.w = V(c->w[0], c->w[1], c->w[2]);
+    o.lens_radius = c->lens_radius; o.time0 = c->time0; o.time1 = c->time1;
+    return o;
+}
+
+int oracle_render_desc(const rt_scene_desc *d, const rt_camera_desc *c, const oracle_params *p, float *out,
+                       oracle_stats *stats) {
+    if (!d || !c || !p || !out) return -1;
+    if (p->nx <= 0 || p->ny <= 0 || p->ns <= 0) return -1;
+    if (p->rng == 0) return -4;   /* the canonical stream belongs to a scene the oracle built itself */
+    scene_t sc;
+    if (scene_from_desc(&sc, d) != 0) { scene_free(&sc); return -2; }
+    cam_t cam = camera_from_desc(c);
+    int rc = render_scene(&sc, &cam, NULL, p, out, stats);
+    scene_free(&sc);
+    return rc;
+}
+
+/* The colour rt_render_features records for a hit (rt_hip.h "first-hit features"). */
+static v3 mat_colour(const hit_t *rec) {
+    const mat_t *m = rec->mat;
+    if (m->kind == MT_METAL) return m->albedo;
+    if (m->kind == MT_DIELECTRIC) return V(1.0f, 1.0f, 1.0f);
+    return tex_value(m->tex, rec->u, rec->v, rec->p);
+}
+
+int oracle_first_hits_desc(const rt_scene_desc *d, const rt_camera_desc *c, const oracle_params *p, int32_t *prim,
+                           float *depth, float *normal, float *albedo) {
+    if (!d || !c || !p || !prim || !depth || !normal || !albedo) return -1;
+    if (p->nx <= 0 || p->ny <= 0 || p->ns <= 0) return -1;
+    int x0 = p->x0, y0 = p->y0, w = p->w, h = p->h;
+    if (w <= 0) { x0 = 0; y0 = 0; w = p->nx; h = p->ny; }
+    if (x0 < 0 || y0 < 0 || x0 + w > p->nx || y0 + h > p->ny) return -3;
+    scene_t sc;
+    if (scene_from_desc(&sc, d) != 0) { scene_free(&sc); return -2; }
+    const cam_t cam = camera_from_desc(c);
+    int nt = p->threads > 0 ? p->threads : 1;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+    for (int row = y0; row < y0 + h; row++) {
+        rng_t g; memset(&g, 0, sizeof g); g.counter = 1;
+        int j = p->ny - 1 - row;
+        for (int i = x0; i < x0 + w; i++) {
+            for (int s = 0; s < p->ns; s++) {
+                rng_seed_sample(&g, sample_key(p->seed, (uint32_t)(j * p->nx + i), (uint32_t)s + p->sample_offset));
+                float u = (float)(i + rng_next(&g)) / (float)p->nx;
+                float v = (float)(j + rng_next(&g)) / (float)p->ny;
+                ray_t r = camera_get_ray(&cam, u, v, &g);
+                hctx_t cx = { &g, 0, 1 };
+                hit_t rec; memset(&rec, 0, sizeof rec);
+                size_t q = ((size_t)(row - y0) * w + (i - x0)) * p->ns + s;
+                if (obj_hit(sc.world, &r, p->tmin, RT_MAXFLOAT, &rec, &cx)) {
+                    v3 a = mat_colour(&rec);
+                    prim[q] = rec.prim;
+                    depth[q] = rec.t * vlen(r.B);
+                    for (int k = 0; k < 3; k++) { normal[3 * q + k] = rec.normal.e[k]; albedo[3 * q + k] = a.e[k]; }
+                } else {
+                    prim[q] = -1;
+                    depth[q] = 0;
+                    for (int k = 0; k < 3; k++) { normal[3 * q + k] = 0; albedo[3 * q + k] = 1.0f; }
+                }
+            }
+        }
+    }
     scene_free(&sc);
     return 0;
 }
@@ -955,8 +1214,8 @@ long oracle_ppm_text(const uint8_t *rgb, int nx, int ny, char *buf, long cap) { 
 void oracle_perlin_tables(float *ranvec, int32_t *perm) {
     rng_t g; memset(&g, 0, sizeof g);
     perlin_generate(&g);
-    for (int i = 0; i < 256; i++) for (int k = 0; k < 3; k++) ranvec[3 * i + k] = g_ranvec[i].e[k];
-    for (int a = 0; a < 3; a++) for (int i = 0; i < 256; i++) perm[256 * a + i] = g_perm[a][i];
+    for (int i = 0; i < 256; i++) for (int k = 0; k < 3; k++) ranvec[3 * i + k] = g_perlin.ranvec[i].e[k];
+    for (int a = 0; a < 3; a++) for (int i = 0; i < 256; i++) perm[256 * a + i] = g_perlin.perm[a][i];
 }
 
 void oracle_drand48(uint64_t x0, int n, double *out) {

@@ -18,6 +18,8 @@
 #define RT_ORACLE_H
 #include <stdint.h>
 
+#include "../include/rt_hip.h"   /* layouts only (rt_scene_desc, rt_camera_desc): nothing of librt_hip is linked */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -34,7 +36,9 @@ enum oracle_scene {
     ORACLE_SCENE_EARTH = 8,         /* main.cpp:87-97 (image set by oracle_set_image) */
     ORACLE_SCENE_EDGE_EMPTY = 9,    /* edge cases of the tests (ref_harness.cpp edge_*):  no objects */
     ORACLE_SCENE_EDGE_SINGLE = 10,  /*   one sphere (the BVH is a single leaf) */
-    ORACLE_SCENE_EDGE_DEGENERATE = 11 /* zero/negative radii, zero-width rect, zero shutter span, density 0 / 1e30 */
+    ORACLE_SCENE_EDGE_DEGENERATE = 11, /* zero/negative radii, zero-width rect, zero shutter span, density 0 / 1e30 */
+    ORACLE_SCENE_EDGE_CHAINS = 12   /*   instance chains (flip between transforms, 6 ops), nested checkers over noise,
+                                         metal / dielectric rects, a medium in a translated sphere */
 };
 
 enum oracle_camera {
@@ -70,6 +74,27 @@ typedef struct oracle_stats {
 /* Renders the rectangle; out_mean = h*w*3 floats of linear mean radiance
  * (after `col /= float(ns)`, before gamma), rows top-down.  Returns 0 on success. */
 int oracle_render(const oracle_params *p, float *out_mean, oracle_stats *stats);
+
+/* The same render of any scene descriptor (include/rt_hip.h) seen through the camera as
+ * given: the object tree is rebuilt from the descriptor (each primitive under its flip and
+ * its instance chain, ops[0] outermost; each medium at its `order` position over the list
+ * of its boundary primitives, its draw ordinal its index), with the descriptor's textures,
+ * materials, images and Perlin tables (copied per call: no process-wide state).  p->scene
+ * and p->camera are ignored; counter RNG only (p->rng == 0 returns -4: the canonical stream
+ * is a property of a scene the oracle built itself).  -2: a malformed descriptor — what
+ * rt_scene_create's validation refuses (missing Perlin tables included), and media whose
+ * `order` decreases along the array: they are "in list order" (rt_hip.h), and a tree built
+ * from unsorted ones would not be the list the fields state. */
+int oracle_render_desc(const rt_scene_desc *d, const rt_camera_desc *cam, const oracle_params *p, float *out_mean,
+                       oracle_stats *stats);
+
+/* First-hit mode: for every camera sample oracle_render_desc traces (same key, jitter, lens
+ * and time draws) the closest surface hit under hitable_list's rule, media skipped — what
+ * rt_render_features averages (rt_hip.h).  Arrays are [h][w][ns] (x 3 for normal, albedo):
+ * prim the index in d->prims (-1 on a miss), depth t * |direction| (0), normal the hit
+ * record's (0, 0, 0), albedo the hit material's colour ((1, 1, 1) on a miss). */
+int oracle_first_hits_desc(const rt_scene_desc *d, const rt_camera_desc *cam, const oracle_params *p, int32_t *prim,
+                           float *depth, float *normal, float *albedo);
 
 /* Quantises a mean-radiance buffer exactly like main.cpp:315-328 into RGB bytes. */
 void oracle_quantize(const float *mean, int n_pixels, uint8_t *rgb);

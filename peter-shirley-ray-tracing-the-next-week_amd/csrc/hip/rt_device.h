@@ -475,10 +475,16 @@ __device__ __forceinline__ Hit prim_record(const float4 *P, const float4 *insts,
         if (kind == RT_PRIM_SPHERE) {
             sphere_uv(h.n, h.u, h.v);   // sphere.h:36: the same (p - center) / radius, before any flip
         } else if (kind != RT_PRIM_MOVING_SPHERE) {                          // aarect.h:54-59
-            float oi, di, oj, dj;
-            if (kind == RT_PRIM_XY_RECT) { oi = r.o.x; di = r.d.x; oj = r.o.y; dj = r.d.y; }
-            else if (kind == RT_PRIM_XZ_RECT) { oi = r.o.x; di = r.d.x; oj = r.o.z; dj = r.d.z; }
-            else { oi = r.o.y; di = r.d.y; oj = r.o.z; dj = r.d.z; }
+            // The rect's two axes by selects, not by a branch per kind.  A workaround, to be removed
+            // with a later compiler: AMD clang 22.0.0git (roc-7.2.0, HIP 7.2.26015) for gfx950 lowers
+            // the chain (xy / xz / else yz: in the optimised IR a correct switch whose default
+            // block has two predecessors) in rt_features so that the default block's copies run
+            // only under the exec mask of the kind <= 1 lanes; the yz lanes kept xy's axes and an
+            // image texture on a yz_rect read the wrong texel.  Guarded by image_rects and
+            // textures_by_kind in tests/test_gpu_generated.py (the feature check).
+            const bool xy = kind == RT_PRIM_XY_RECT, yz = kind == RT_PRIM_YZ_RECT;
+            const float oi = yz ? r.o.y : r.o.x, di = yz ? r.d.y : r.d.x;
+            const float oj = xy ? r.o.y : r.o.z, dj = xy ? r.d.y : r.d.z;
             const float a = oi + t * di, b = oj + t * dj;
             h.u = (a - g0.x) / (g0.y - g0.x);
             h.v = (b - g0.z) / (g0.w - g0.z);

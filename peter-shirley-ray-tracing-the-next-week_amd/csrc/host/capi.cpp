@@ -285,6 +285,10 @@ static int validate_desc(const rt_scene_desc *d) {
         const rt_medium &m = d->media[i];
         if (m.boundary_first < 0 || m.boundary_count < 0 || m.boundary_first + m.boundary_count > d->nboundary)
             return fail(RT_ERR_INVALID, "medium boundary range out of range");
+        // the device reads a medium's first boundary record unconditionally (load_media,
+        // media_hit); dropping the medium instead would renumber the others' draw ordinals
+        if (m.boundary_count == 0)
+            return fail(RT_ERR_UNSUPPORTED, "medium " + std::to_string(i) + " has no boundary primitive (boundary_count 0)");
         if (m.material < 0 || m.material >= d->nmaterials) return fail(RT_ERR_INVALID, "medium material out of range");
     }
     for (int i = 0; i < d->ninstances; i++) {

@@ -422,6 +422,39 @@ hitable *edge_degenerate() {
     return new hitable_list(l, i);
 }
 
+// Instance chains (a sphere and a moving sphere under translate(rotate_y), a flip_normals
+// between two transforms, a chain of 6), a checker of checkers over a noise texture, a metal
+// and a dielectric xz_rect, a constant_medium in a translated sphere, one light.
+hitable *edge_chains() {
+    hitable **l = new hitable *[12];
+    int i = 0;
+    texture *noise = new noise_texture(2);
+    texture *nested = new checker_texture(new checker_texture(new constant_texture(vec3(0.9, 0.1, 0.1)), noise),
+                                          new checker_texture(noise, new constant_texture(vec3(0.1, 0.1, 0.9))));
+    material *white = new lambertian(new constant_texture(vec3(0.73, 0.73, 0.73)));
+    material *glass = new dielectric(1.5);
+    l[i++] = new xz_rect(-6, 6, -6, 6, 0, new lambertian(nested));                       // checker of checkers over noise
+    l[i++] = new translate(new rotate_y(new sphere(vec3(0, 0, 0), 0.6, white), 30), vec3(-2, 0.6, 0));
+    l[i++] = new translate(new rotate_y(new moving_sphere(vec3(0, 0, 0), vec3(0.3, 0.2, 0), 0, 1, 0.5,
+                                                          new lambertian(new constant_texture(vec3(0.2, 0.8, 0.2)))), -20),
+                           vec3(2, 0.5, 0.5));
+    l[i++] = new translate(new flip_normals(new rotate_y(new xy_rect(-0.8, 0.8, 0, 1.2, 0,   // a flip between two transforms
+                                                                     new lambertian(new constant_texture(vec3(0.8, 0.3, 0.3)))), 25)),
+                           vec3(0, 0, -2));
+    l[i++] = new translate(new rotate_y(new translate(new flip_normals(new rotate_y(new translate(   // a chain of 6
+                 new sphere(vec3(0, 0, 0), 0.4, new lambertian(noise)), vec3(0.2, 0, 0)), 40)), vec3(0, 0.1, 0.3)), -15),
+                           vec3(-0.5, 0.4, 1.2));
+    l[i++] = new xz_rect(-1.8, -0.6, 1.8, 3, 0.3, new metal(vec3(0.8, 0.8, 0.9), 0.0));
+    l[i++] = new xz_rect(0.6, 1.8, 1.8, 3, 0.3, glass);
+    l[i++] = new constant_medium(new translate(new sphere(vec3(0, 0, 0), 0.7, glass), vec3(0.8, 0.8, -0.5)), 1.5,
+                                 new constant_texture(vec3(0.9, 0.9, 0.9)));
+    l[i++] = new translate(new rotate_y(new box(vec3(0, 0, 0), vec3(0.7, 0.9, 0.7), white), -18), vec3(3, 0, -1.5));
+    l[i++] = new sphere(vec3(3.2, 0.45, 1.6), 0.45, glass);
+    l[i++] = new moving_sphere(vec3(-3.2, 0.4, 1.5), vec3(-3.2, 0.7, 1.5), 0, 1, 0.4, new metal(vec3(0.9, 0.7, 0.5), 0.2));
+    l[i++] = new xz_rect(-1, 1, -1, 1, 4, new diffuse_light(new constant_texture(vec3(6, 6, 6))));
+    return new hitable_list(l, i);
+}
+
 hitable *build_named_scene(const std::string &name, float *time0, float *time1) {
     reset_reference_rng();
     *time0 = 0.0f;
@@ -437,6 +470,7 @@ hitable *build_named_scene(const std::string &name, float *time0, float *time1) 
     if (name == "edge_empty") return edge_empty();
     if (name == "edge_single") return edge_single();
     if (name == "edge_degenerate") return edge_degenerate();
+    if (name == "edge_chains") return edge_chains();
     if (name == "earth") {
         const char *png = std::getenv("RTNW_EARTH_PNG");
         return earth(png ? png : "picture.png");

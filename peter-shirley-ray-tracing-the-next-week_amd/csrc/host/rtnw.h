@@ -400,6 +400,7 @@ hitable *two_spheres();          // main.cpp:99-110
 hitable *edge_empty();           // the tests' edge scenes (oracle/ref_harness.cpp edge_*)
 hitable *edge_single();
 hitable *edge_degenerate();
+hitable *edge_chains();
 hitable *simple_light();         // main.cpp:122-133
 hitable *test_scene();           // main.cpp:135-145 (`test`)
 hitable *cornell_box();          // main.cpp:148-166

@@ -63,6 +63,10 @@ class RtMedium(ctypes.Structure):
                 ("material", ctypes.c_int32), ("order", ctypes.c_int32), ("pad", ctypes.c_int32 * 3)]
 
 
+class RtImage(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("nx", ctypes.c_int32), ("ny", ctypes.c_int32)]
+
+
 class RtSceneDesc(ctypes.Structure):
     _fields_ = [("abi_version", ctypes.c_uint32), ("nprims", ctypes.c_int32), ("nboundary", ctypes.c_int32),
                 ("nmedia", ctypes.c_int32), ("nmaterials", ctypes.c_int32), ("ntextures", ctypes.c_int32),
@@ -71,7 +75,9 @@ class RtSceneDesc(ctypes.Structure):
                 ("media", ctypes.POINTER(RtMedium)), ("materials", ctypes.POINTER(RtMaterial)),
                 ("textures", ctypes.POINTER(RtTexture)), ("instances", ctypes.POINTER(RtInstance)),
                 ("perlin_ranvec", ctypes.POINTER(ctypes.c_float)), ("perlin_perm", ctypes.POINTER(ctypes.c_int32)),
-                ("time0", ctypes.c_float), ("time1", ctypes.c_float)]
+                ("time0", ctypes.c_float), ("time1", ctypes.c_float),
+                ("nimages", ctypes.c_int32), ("images", ctypes.POINTER(RtImage)),
+                ("image_data", ctypes.POINTER(ctypes.c_uint8)), ("image_bytes", ctypes.c_int64)]
 
 
 class RtCameraDesc(ctypes.Structure):
@@ -297,6 +303,7 @@ SCENE_DEFAULTS = {   # per-scene camera / background / depth pairing (SURVEY §8
     "edge_empty": ("random", RT_BG_SKY, 50),        # the tests' edge scenes (oracle/ref_harness.cpp edge_*)
     "edge_single": ("random", RT_BG_SKY, 50),
     "edge_degenerate": ("random", RT_BG_SKY, 50),
+    "edge_chains": ("random", RT_BG_SKY, 50),
     "test": ("random", RT_BG_BLACK, 50),
     "earth": ("cornell", RT_BG_BLACK, 50),
 }
@@ -308,11 +315,50 @@ def RenderParams(nx, ny, spp, max_depth=50, t_min=0.001, background=RT_BG_BLACK,
                           chunk=chunk, flags=flags, sample_offset=sample_offset, seed=seed)
 
 
-class SceneDesc:
-    """A flattened scene built by the host API (owned by librt_hip)."""
+RT_ABI_VERSION = 2
 
-    def __init__(self, ptr):
+
+class SceneDesc:
+    """A flattened scene: built by the host API (owned by librt_hip), or from_arrays (owned by
+    this object)."""
+
+    def __init__(self, ptr, keep=None):
         self.ptr = ptr
+        self._keep = keep   # from_arrays: the numpy arrays and the struct the pointers lead into
+
+    @classmethod
+    def from_arrays(cls, *, prims, materials, textures, perlin_ranvec, perlin_perm, boundary_prims=(), media=(),
+                    instances=(), images=(), image_data=b"", time0=0.0, time1=1.0) -> "SceneDesc":
+        """A descriptor over arrays this object owns.  prims, boundary_prims, media, materials,
+        textures, instances and images are sequences of RtPrim, RtMedium, RtMaterial, RtTexture,
+        RtInstance and RtImage; perlin_ranvec is 256 x 3 float32, perlin_perm 3 x 256 int32;
+        image_data the texel bytes of all images.  The arrays live as long as the object and are
+        never handed to rt_scene_desc_free."""
+        def arr(items, T):
+            a = (T * max(1, len(items)))()
+            for i, x in enumerate(items):
+                a[i] = x
+            return a, len(items)
+        keep = {}
+        d = RtSceneDesc(abi_version=RT_ABI_VERSION, time0=time0, time1=time1)
+        for field, count, items, T in (("prims", "nprims", prims, RtPrim), ("boundary_prims", "nboundary", boundary_prims, RtPrim),
+                                       ("media", "nmedia", media, RtMedium), ("materials", "nmaterials", materials, RtMaterial),
+                                       ("textures", "ntextures", textures, RtTexture),
+                                       ("instances", "ninstances", instances, RtInstance), ("images", "nimages", images, RtImage)):
+            a, n = arr(list(items), T)
+            keep[field] = a
+            setattr(d, field, ctypes.cast(a, ctypes.POINTER(T)))
+            setattr(d, count, n)
+        rv = np.ascontiguousarray(perlin_ranvec, dtype=np.float32).reshape(768)
+        pm = np.ascontiguousarray(perlin_perm, dtype=np.int32).reshape(768)
+        tx = np.frombuffer(bytes(image_data) or b"\0", dtype=np.uint8).copy()
+        keep.update(ranvec=rv, perm=pm, texels=tx)
+        d.perlin_ranvec = rv.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        d.perlin_perm = pm.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        d.image_data = tx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        d.image_bytes = len(image_data)
+        keep["desc"] = d
+        return cls(ctypes.pointer(d), keep)
 
     @classmethod
     def builtin(cls, name: str, earth_png: str | None = None) -> "SceneDesc":
@@ -335,9 +381,9 @@ class SceneDesc:
         return self.ptr.contents
 
     def free(self):
-        if self.ptr:
+        if self.ptr and self._keep is None:
             lib().rt_scene_desc_free(self.ptr)
-            self.ptr = None
+        self.ptr = None
 
     def __del__(self):
         try:

@@ -170,7 +170,7 @@ int main() {
     setvbuf(stdout, nullptr, _IONBF, 0);
     int bad = 0;
     const char *names[] = {"final", "random_scene", "cornell_box", "cornell_smoke", "random_motion", "simple_light",
-                           "test", "two_spheres", "edge_empty", "edge_single", "edge_degenerate"};
+                           "test", "two_spheres", "edge_empty", "edge_single", "edge_degenerate", "edge_chains"};
     for (const char *nm : names) {
         rt_scene_desc *d = nullptr;
         if (rt_builtin_scene_desc(nm, &d) != 0) { std::printf("%s: %s\n", nm, rt_last_error()); return 2; }

@@ -97,6 +97,7 @@ CASES = [   # (scene, nx, ny, spp, chunk, seed)  — c1..c4 of BASELINE.json at 
     ("edge_empty", 16, 8, 2, 2, 10),        # no objects: no BVH, every ray is background
     ("edge_single", 32, 16, 8, 8, 11),      # one sphere: the BVH root is a leaf
     ("edge_degenerate", 40, 20, 16, 16, 12),   # zero/negative radii, zero-width rect, 0/0 shutter, density 0 and 1e30
+    ("edge_chains", 40, 20, 8, 8, 13),      # chains with a flip between transforms and of 6 ops, nested checkers over noise
 ]
 
 
@@ -191,7 +192,7 @@ def test_gpu_matches_oracle_at_parameter_edges(scene, nx, ny, ns, chunk, depth, 
 
 
 @pytest.mark.parametrize("name", ["c1_random", "c2_cornell", "c3_motion", "c4_final", "smoke", "simple_light",
-                                  "earth", "edge_empty", "edge_single", "edge_degenerate"])
+                                  "earth", "edge_empty", "edge_single", "edge_degenerate", "edge_chains"])
 def test_gpu_matches_reference_framebuffer(golden, name):
     """Against the reference's own counter-RNG output (golden, made by the reference binary)."""
     c = golden["counter_fb"][name]
@@ -462,7 +463,7 @@ def test_ppm_from_gpu_mean_matches_oracle_quantiser():
 @pytest.mark.parametrize("scene,nx,ny,ns", [("final", 48, 48, 16), ("cornell_smoke", 32, 32, 8),
                                             ("random_motion", 40, 20, 8), ("earth", 32, 32, 8),
                                             ("edge_empty", 16, 8, 2), ("edge_single", 24, 12, 4),
-                                            ("edge_degenerate", 40, 20, 8)])
+                                            ("edge_degenerate", 40, 20, 8), ("edge_chains", 40, 20, 8)])
 def test_bvh_widths_agree_bitwise(monkeypatch, scene, nx, ny, ns):
     """The closest hit is fixed by (t, list order) whatever structure finds it: the
     BVH's node form (RTNW_BVH_WIDTH = 2, 4, 8 or 8q (compressed 8-wide) at scene

@@ -58,7 +58,7 @@ def check_against_oracle(what, g, o):
 
 # ---- 1. the reference executable's framebuffers, bit for bit ---------------------------
 @pytest.mark.parametrize("name", ["c1_random", "c2_cornell", "c3_motion", "c4_final", "smoke", "simple_light",
-                                  "earth", "edge_empty", "edge_single", "edge_degenerate"])
+                                  "earth", "edge_empty", "edge_single", "edge_degenerate", "edge_chains"])
 def test_right_fold_equals_the_reference_framebuffer_bitwise(golden, name):
     c = golden["counter_fb"][name]
     ref = np.load(os.path.join(GOLDEN, f"ref_{name}.npy"))
