@@ -1,5 +1,5 @@
 // rt_denoise.h — launch interface of rt_denoise.hip: the variance-guided edge-avoiding
-// à-trous filter (capi.cpp rt_denoise, rt_denoise_dev).  Internal to
+// à-trous filter (capi_post.cpp rt_denoise, rt_denoise_dev).  Internal to
 // librt_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,10 +25,10 @@ extern "C" hipError_t rt_launch_denoise_atrous(int nx, int ny, int step, float s
                                                float4 *E_out, const float *guides, int demodulate, float *out_rgb,
                                                hipStream_t stream);
 
-// capi.cpp reaches the launchers through this table, filled by rt_denoise.hip's static
+// capi_post.cpp reaches the launchers through this table, filled by rt_denoise.hip's static
 // initialiser when the unit is linked in (like rt_moments.h's RtMomentsLaunch).
 struct RtDenoiseLaunch {
     decltype(&rt_launch_denoise_prepare) prepare;
     decltype(&rt_launch_denoise_atrous) atrous;
 };
-extern "C" RtDenoiseLaunch rt_denoise_launch;   // defined (empty) in capi.cpp
+extern "C" RtDenoiseLaunch rt_denoise_launch;   // defined (empty) in capi_post.cpp

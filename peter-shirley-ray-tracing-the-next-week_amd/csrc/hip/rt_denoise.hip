@@ -153,6 +153,6 @@ extern "C" hipError_t rt_launch_denoise_atrous(int nx, int ny, int step, float s
     return hipGetLastError();
 }
 
-// the unit announces its launchers to capi.cpp when it is linked in
+// the unit announces its launchers to the host when it is linked in
 static const bool denoise_unit_linked =
     (rt_denoise_launch = RtDenoiseLaunch{rt_launch_denoise_prepare, rt_launch_denoise_atrous}, true);

@@ -1541,7 +1541,7 @@ __device__ __forceinline__ ShadeState shade_begin(const RtKernelArgs &A, bool re
         st.live = depth < A.max_depth;
         const bool textured = st.kind == RT_MAT_DIFFUSE_LIGHT ||
                               (st.live && (st.kind == RT_MAT_LAMBERTIAN || st.kind == RT_MAT_ISOTROPIC));
-        if (textured && (fbits(m1.w) & 2)) {   // a constant texture, resolved by the host (capi.cpp)
+        if (textured && (fbits(m1.w) & 2)) {   // a constant texture, resolved by the host (scene_lower.cpp)
             st.tv = mk(m1.x, m1.y, m1.z);
         } else if (textured) {
             float4 t0, t1;

@@ -1,5 +1,5 @@
 // rt_features.h — launch interface of rt_features.hip: the first-hit feature pass
-// (albedo, normal, depth, coverage per pixel; capi.cpp rt_render_features,
+// (albedo, normal, depth, coverage per pixel; capi_post.cpp rt_render_features,
 // rt_render_features_dev).  Internal to librt_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,11 +24,11 @@ extern "C" hipError_t rt_launch_features(const RtKernelArgs *a, int x0, int y0, 
 extern "C" hipError_t rt_launch_features_resolve(const float *slab, uint32_t npix, int ns, float k, int first, int last,
                                                  float *guides, hipStream_t stream);
 
-// capi.cpp reaches the launchers through this table, which rt_features.hip's static
+// capi_post.cpp reaches the launchers through this table, which rt_features.hip's static
 // initialiser fills when the unit is linked in (like rt_moments.h's RtMomentsLaunch): a
 // library linked without it returns RT_ERR_UNSUPPORTED from the feature entry points.
 struct RtFeaturesLaunch {
     decltype(&rt_launch_features) sample;
     decltype(&rt_launch_features_resolve) resolve;
 };
-extern "C" RtFeaturesLaunch rt_features_launch;   // defined (empty) in capi.cpp
+extern "C" RtFeaturesLaunch rt_features_launch;   // defined (empty) in capi_post.cpp

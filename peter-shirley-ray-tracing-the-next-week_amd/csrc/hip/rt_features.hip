@@ -108,7 +108,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_features(const RtKernelArgs A, in
             for (uint32_t q = 0; q < n; ++q) test(q);
     } else {
         if (valid)
-            for (uint32_t q = 0; q < (uint32_t)A.nprescan; ++q) test(q);   // kept out of the BVH (capi.cpp)
+            for (uint32_t q = 0; q < (uint32_t)A.nprescan; ++q) test(q);   // kept out of the BVH (scene_lower.cpp)
         const GlobalNodes gnodes{A.nodes};
         const Slab sl = make_slab<0>(r, A.tmin);
         Counters cnt;
@@ -182,6 +182,6 @@ extern "C" hipError_t rt_launch_features_resolve(const float *slab, uint32_t npi
     return hipGetLastError();
 }
 
-// the unit announces its launchers to capi.cpp when it is linked in
+// the unit announces its launchers to the host when it is linked in
 static const bool features_unit_linked =
     (rt_features_launch = RtFeaturesLaunch{rt_launch_features, rt_launch_features_resolve}, true);

@@ -1,4 +1,4 @@
-// rt_kernel.h — launch interface between the host runtime (capi.cpp) and the
+// rt_kernel.h — launch interface between the host runtime (capi_*.cpp) and the
 // megakernel (rt_kernel.hip).  Internal to librt_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,7 +52,7 @@ struct RtKernelArgs {
     uint32_t nprims;        // surface primitives (flat scan: all copied to LDS)
     int nprescan;           // BVH modes: primitives [0, nprescan) are outside the BVH, tested first in lockstep
     int cell_first, cell_n;   // BVH modes: the medium cell's primitive copies [cell_first, cell_first + cell_n) ...
-    float cell_c[3], cell_r2; //     ... and its ball (centre, squared radius): capi.cpp rt_scene_create ...
+    float cell_c[3], cell_r2; //     ... and its ball (centre, squared radius): scene_lower.cpp medium_cell ...
     float cell_rin2;          //     ... and the squared radius inside which a ray counts as inside whatever its direction
     int ball_waves;           // waves per workgroup that take the medium cell's paths first (LDS media variant) ...
     int ball_batch;           //     ... their ready batch (the others': RT_READY_BATCH) ...
@@ -79,7 +79,7 @@ struct RtKernelArgs {
     uint32_t npix;
     uint32_t nitems;          // npix * nchunks
     uint32_t ndeep;           // the job's first ndeep pixels are claimed first, all their chunks ...
-    uint32_t ndeep_items;     // ... (ndeep * nchunks items), then the other pixels' (capi.cpp prepare_job)
+    uint32_t ndeep_items;     // ... (ndeep * nchunks items), then the other pixels' (capi_render.cpp prepare_job)
     uint32_t claim;           // work items per wave-level claim (a multiple of 64) ...
     uint32_t nbig;            // ... for the first nbig claims; the rest (the launch's tail) claim
     uint32_t claim_tail;      //     claim_tail items each, so that waves run dry together
@@ -103,7 +103,7 @@ typedef hipError_t (*RtFoldLaunch)(const RtKernelArgs *a, int grid, hipStream_t 
 extern "C" hipError_t rt_launch_megakernel(const RtKernelArgs *a, int grid, int mode, hipStream_t stream);
 // 1 when the library holds the fold unit (a library linked from rt_kernel.o alone does not)
 extern "C" int rt_megakernel_has_fold(void);
-// Resolve of one sample batch (capi.cpp): adds the batch's partial sums to each
+// Resolve of one sample batch (capi_render.cpp): adds the batch's partial sums to each
 // pixel's running sum in sample order.  mode: RT_RESOLVE_* bits.
 #define RT_RESOLVE_FIRST 1    // the first batch: start from 0 (or, with SUM_IN, from out)
 #define RT_RESOLVE_LAST 2     // the last batch: write out (times k unless RAW), else keep acc

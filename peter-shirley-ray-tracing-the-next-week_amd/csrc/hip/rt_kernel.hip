@@ -313,7 +313,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         const uint32_t n = min(64u, pool_end - pool_next);
         if (kProf) rt_items += n;
         if (lane < n) {
-            // item -> (sample chunk c, job pixel p): the job's first ndeep pixels (capi.cpp:
+            // item -> (sample chunk c, job pixel p): the job's first ndeep pixels (capi_render.cpp:
             // those whose primary rays enter a dense medium) have all their chunks first,
             // sample-major, then the other pixels' (RtKernelArgs.ndeep)
             const uint32_t it = pool_next + lane;
@@ -660,7 +660,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                 if (act) phase = PH_READY;
             }
         } else {
-            // the medium cell (capi.cpp): a new segment starting inside the ball tests the
+            // the medium cell (scene_lower.cpp): a new segment starting inside the ball tests the
             // primitives near it; a hit before the ray leaves the ball is the closest of
             // all (every other primitive lies outside), and the search ends without a descent
             if (kCell && ballrole && A.cell_n > 0) {
@@ -695,7 +695,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                 // the pool and a ball wave forever when no normal wave is left
                 if (A.ball_park && !exhausted && fr && phase == PH_TRAV) phase = PH_PARK;
             }
-            // pre-scan: the scene's largest primitives (capi.cpp), kept out of the BVH,
+            // pre-scan: the scene's largest primitives (scene_lower.cpp), kept out of the BVH,
             // tested in lockstep by every lane with a new segment before its descent;
             // their hits also shorten best_t, which culls more of the BVH
             if (kPrescan && A.nprescan > 0) {
@@ -964,7 +964,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
 // Adds one sample batch's partial sums to each pixel's running sum, in sample
 // order (main.cpp:311 `col += temp`, one add per sample with one sample per work
 // item), so the image does not depend on how the samples were split into batches
-// (capi.cpp bounds the slab per launch).  The last batch applies `col /= float(ns)`
+// (capi_render.cpp bounds the slab per launch).  The last batch applies `col /= float(ns)`
 // as the reciprocal multiply of vec3.h:134-141.
 __global__ __launch_bounds__(256) void rt_resolve(const float *__restrict__ slab, uint32_t npix, int nchunks, float k,
                                                   float4 *__restrict__ acc, int mode,
@@ -1070,7 +1070,7 @@ static hipError_t launch_one(const RtKernelArgs *a, int grid, hipStream_t stream
 template <int kWidth, int kFeat, int kLds>
 static hipError_t launch_variant(const RtKernelArgs *a, int grid, int mode, hipStream_t stream) {
 #ifdef MEGAKERNEL_FOLD_UNIT
-    // the right-fold variants (rt_megakernel kFold): plain mode, width 2 (capi.cpp checks both)
+    // the right-fold variants (rt_megakernel kFold): plain mode, width 2 (capi_render.cpp checks both)
     if constexpr (kWidth == 2)
         if (mode == RT_LAUNCH_FOLD) return launch_one<false, false, kWidth, kFeat, kLds, true>(a, grid, stream);
     return hipErrorInvalidValue;

@@ -1,5 +1,5 @@
 // rt_moments.h — launch interface of rt_moments.hip: the resolve that also keeps each
-// pixel's moments, and the adaptive driver's select / test / guard / finish kernels (capi.cpp
+// pixel's moments, and the adaptive driver's select / test / guard / finish kernels (capi_adaptive.cpp
 // rt_render_tiles_moments, rt_render_adaptive, rt_render_adaptive_guarded).  Internal to
 // librt_hip.so.
 #pragma once
@@ -41,7 +41,7 @@ extern "C" hipError_t rt_launch_adaptive_guard(int w, int h, int r, const uint8_
 // sample count (vec3.h:134-141, as rt_resolve's last batch does with the job's one count).
 extern "C" hipError_t rt_launch_adaptive_finish(uint32_t npix, const int32_t *spp, float *sums, hipStream_t stream);
 
-// capi.cpp reaches the launchers through this table, which rt_moments.hip's static
+// The host reaches the launchers through this table, which rt_moments.hip's static
 // initialiser fills when the unit is linked in (like rt_kernel.h's rt_fold_launch): the host
 // objects still link against rt_kernel.o alone, and the moments / adaptive entry points of
 // such a library return RT_ERR_UNSUPPORTED.
@@ -52,4 +52,4 @@ struct RtMomentsLaunch {
     decltype(&rt_launch_adaptive_test) test;
     decltype(&rt_launch_adaptive_guard) guard;
 };
-extern "C" RtMomentsLaunch rt_moments_launch;   // defined (empty) in capi.cpp
+extern "C" RtMomentsLaunch rt_moments_launch;   // defined (empty) in capi_adaptive.cpp

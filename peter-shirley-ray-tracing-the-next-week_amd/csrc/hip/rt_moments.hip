@@ -210,7 +210,7 @@ extern "C" hipError_t rt_launch_adaptive_finish(uint32_t npix, const int32_t *sp
     return hipGetLastError();
 }
 
-// the unit announces its launchers to capi.cpp when it is linked in
+// the unit announces its launchers to the host when it is linked in
 static const bool moments_unit_linked =
     (rt_moments_launch = RtMomentsLaunch{rt_launch_resolve_moments, rt_launch_adaptive_select, rt_launch_adaptive_finish,
                                          rt_launch_adaptive_test, rt_launch_adaptive_guard},

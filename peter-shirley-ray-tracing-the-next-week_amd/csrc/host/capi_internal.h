@@ -1,0 +1,112 @@
+// capi_internal.h — what the units of the C ABI (capi_*.cpp) share: the scene object, the
+// error helpers, the grow-on-demand buffers and the launch-argument fillers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "rt_hip.h"
+#include "../rt_layout.h"
+#include "../hip/rt_kernel.h"
+#include "scene_lower.h"
+
+inline int fail(int code, const std::string &msg) { return rt_internal_fail(code, msg); }
+inline int hip_fail(hipError_t e, const char *what) {
+    return fail(RT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define HIP_TRY(expr)                                   \
+    do {                                                \
+        hipError_t e_ = (expr);                         \
+        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+
+inline int env_int(const char *name, int dflt, int lo, int hi) {
+    if (const char *e = std::getenv(name)) return std::max(lo, std::min(hi, std::atoi(e)));
+    return dflt;
+}
+
+// A device buffer kept between calls and grown on demand (the old allocation is freed
+// first; it never shrinks), and its sibling in pinned host memory.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t n) {
+        if (n <= bytes) return RT_OK;
+        release();
+        HIP_TRY(hipMalloc(&p, n));
+        bytes = n;
+        return RT_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+struct PinBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    int reserve(size_t n) {
+        if (n <= bytes) return RT_OK;
+        release();
+        HIP_TRY(hipHostMalloc(&p, n, hipHostMallocDefault));
+        bytes = n;
+        return RT_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+struct rt_scene : rtnw::SceneInfo {
+    int device = 0;
+    int cus = 0;
+    int grid[3] = {0, 0, 0};      // persistent megakernel grid per variant (plain, count, profile)
+    bool lds_nodes = false;       // the BVH2 fits the LDS variant (one RT_LDS_BLOCK workgroup per CU)
+    int stack_depth = 0;          // its traversal stack entries per lane
+    hipStream_t own_stream = nullptr;
+    // scene in HBM: one allocation (arena) holding the arrays below (rtnw::LoweredScene's image)
+    void *arena = nullptr;
+    void *nodes = nullptr, *prims = nullptr, *bprims = nullptr, *media = nullptr, *mats = nullptr, *texs = nullptr,
+         *insts = nullptr, *ranvec = nullptr, *perm = nullptr, *texels = nullptr, *groups = nullptr;
+    // job cache
+    std::vector<int32_t> job_tiles;
+    uint32_t job_ndeep = 0;                 // the job's first job_ndeep pixels are the deep ones (prepare_job)
+    uint32_t npix = 0;
+    void *job_xy = nullptr, *job_out = nullptr;
+    size_t job_cap = 0;           // pixels job_xy and job_out have room for
+    DevBuf slab;
+    DevBuf acc;                   // per-pixel running sums between sample batches
+    DevBuf frame;                 // rt_render_adaptive: the frame's sums, moments, counts and flags ...
+    PinBuf pin;                   // ... and pinned host memory for the passes' pixel lists, flags and counters
+    DevBuf fold;                  // RT_FLAG_RIGHT_FOLD: the lanes' attenuation stacks (rt_kernel.h RtKernelArgs.fold)
+    void *counter = nullptr, *stats = nullptr;
+    DevBuf host_out;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
+// internal to the library: not among its dynamic symbols
+#pragma GCC visibility push(hidden)
+
+// capi_scene.cpp
+int scene_features(const rt_scene *s);
+int ensure_own_stream(rt_scene *s);   // created on first use (rt_scene_create)
+
+// capi_render.cpp
+void fill_scene_args(const rt_scene *s, RtKernelArgs &a);
+void fill_camera_args(const rt_camera_desc *cam, const rt_render_params *p, RtKernelArgs &a);
+bool deep_first(const rt_scene *s);
+bool deep_pixel(const rt_scene *s, const rt_camera_desc *cam, int x, int y, int nx, int ny);
+struct JobSlots {
+    const uint32_t *xy, *slot;
+    uint32_t n, ndeep;
+};
+int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
+               const JobSlots *js, float *out_dev, float *mom_dev, void *stream_v, rt_stats *stats);
+
+#pragma GCC visibility pop

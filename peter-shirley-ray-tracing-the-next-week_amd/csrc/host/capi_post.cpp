@@ -1,0 +1,213 @@
+// capi_post.cpp — what runs beside a render: the first-hit feature buffers (rt_features.hip)
+// and the à-trous denoiser (rt_denoise.hip).
+#include <map>
+#include <mutex>
+
+#include "capi_internal.h"
+#include "../hip/rt_features.h"
+#include "../hip/rt_denoise.h"
+
+// the units' launchers, set by their static initialisers (rt_features.h, rt_denoise.h)
+RtFeaturesLaunch rt_features_launch = {nullptr, nullptr};
+RtDenoiseLaunch rt_denoise_launch = {nullptr, nullptr};
+
+// ------------------------------------------------ first-hit features (rt_hip.h)
+// The argument checks of both entry points, the scene's last: all before any HIP call.
+static int features_check(const char *fn, const rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0,
+                          int y0, int w, int h, bool have_out) {
+    const std::string f(fn);
+    if (!cam || !p) return fail(RT_ERR_INVALID, f + ": null argument (cam or params)");
+    if (!have_out) return fail(RT_ERR_INVALID, f + ": null output (at least one feature buffer is needed)");
+    if (p->nx < 1 || p->ny < 1 || p->nx > 65535 || p->ny > 65535)
+        return fail(RT_ERR_INVALID, f + ": nx and ny must be in 1..65535");
+    if (p->spp < 1) return fail(RT_ERR_INVALID, f + ": spp must be at least 1");
+    if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE | RT_FLAG_SUM_IN | RT_FLAG_SUM_OUT))
+        return fail(RT_ERR_INVALID, f + ": RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
+    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > p->nx - w || y0 > p->ny - h)
+        return fail(RT_ERR_INVALID, f + ": rectangle (x0, y0, w, h) empty or outside the image");
+    if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
+    if (s->bvh_width != 2)
+        return fail(RT_ERR_UNSUPPORTED, f + " needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
+    if (!rt_features_launch.sample)
+        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the features unit (rt_features.o)");
+    if (s->has_moving && (cam->time0 < s->time0 || cam->time1 > s->time1))
+        return fail(RT_ERR_INVALID, f + ": camera shutter outside the scene's time span (moving-sphere bounds)");
+    return RT_OK;
+}
+
+// Slab bytes of one feature launch: the samples of a job run in batches of whole samples
+// that fit it, each batch added to the running sums in guides_dev in sample order.
+#define RT_FEATURE_SLAB_BYTES (256ull << 20)
+
+static int features_run(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
+                        float *guides_dev, hipStream_t stream) {
+    const uint32_t npix = (uint32_t)w * (uint32_t)h;   // <= 65535^2
+    const uint64_t sample_bytes = (uint64_t)npix * RT_GUIDE_FLOATS * sizeof(float);
+    uint64_t per = std::max<uint64_t>(1, RT_FEATURE_SLAB_BYTES / sample_bytes);
+    per = std::min<uint64_t>(per, std::max<uint64_t>(1, 0x7FFFFFFFull / npix));
+    per = std::min<uint64_t>(per, (uint64_t)p->spp);
+    if ((uint64_t)npix * per >= 0x80000000ull) return fail(RT_ERR_INVALID, "rt_render_features: rectangle too large");
+    if (int rc = s->slab.reserve((size_t)(sample_bytes * per))) return rc;
+    // the pass reads the scene's arrays and the camera (rt_features.hip), none of the
+    // megakernel's launch knobs
+    RtKernelArgs a{};
+    fill_scene_args(s, a);
+    fill_camera_args(cam, p, a);
+    a.npix = npix;
+    const float k = (float)(1.0 / (double)(float)p->spp);   // vec3.h:134-141, as rt_resolve
+    for (uint64_t s0 = 0; s0 < (uint64_t)p->spp; s0 += per) {
+        const uint64_t s1 = std::min<uint64_t>(s0 + per, (uint64_t)p->spp);
+        a.ns = (int)(s1 - s0);
+        a.sample_offset = p->sample_offset + (uint32_t)s0;
+        HIP_TRY(rt_features_launch.sample(&a, x0, y0, w, (float *)s->slab.p, stream));
+        HIP_TRY(rt_features_launch.resolve((const float *)s->slab.p, npix, a.ns, k, s0 == 0, s1 == (uint64_t)p->spp,
+                                           guides_dev, stream));
+    }
+    return RT_OK;
+}
+
+// ------------------------------------------------ denoiser (rt_hip.h)
+static int denoise_check(const char *fn, int nx, int ny, bool nulls, const rt_denoise_params *dp, bool moments, bool spp) {
+    const std::string f(fn);
+    if (nulls || !dp) return fail(RT_ERR_INVALID, f + ": null argument");
+    if (nx < 1 || ny < 1 || (uint64_t)nx * (uint64_t)ny > 0x7FFFFFFFull)
+        return fail(RT_ERR_INVALID, f + ": nx and ny must be at least 1 (and nx * ny below 2^31)");
+    if (dp->iterations < 0 || dp->iterations > 8) return fail(RT_ERR_INVALID, f + ": iterations must be in 0..8");
+    if (!(dp->sigma_color >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_color must not be negative or NaN");
+    if (!(dp->sigma_depth >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_depth must not be negative or NaN");
+    if (moments && !spp && dp->uniform_spp < 1)
+        return fail(RT_ERR_INVALID, f + ": uniform_spp must be at least 1 when moments come without an spp map");
+    if (dp->variance_filter != 0 && dp->variance_filter != 1)
+        return fail(RT_ERR_INVALID, f + ": variance_filter must be 0 or 1");
+    if (!rt_denoise_launch.prepare)
+        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the denoise unit (rt_denoise.o)");
+    return RT_OK;
+}
+
+// The filter's planes (G, E ping, E pong: 48 B per pixel) per device, grown on demand.
+namespace {
+struct DenoiseWorkspace { void *p = nullptr; size_t bytes = 0; };
+std::mutex g_dn_mu;
+std::map<int, DenoiseWorkspace> g_dn_ws;
+}
+
+static int denoise_run(int device, int nx, int ny, const float *color, const float *guides, const float *moments,
+                       const int32_t *spp, const rt_denoise_params *dp, float *out, hipStream_t stream) {
+    const size_t npix = (size_t)nx * ny;
+    if (dp->iterations == 0) {   // the input, as it is
+        HIP_TRY(hipMemcpyAsync(out, color, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        return RT_OK;
+    }
+    float4 *planes = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_dn_mu);
+        DenoiseWorkspace &ws = g_dn_ws[device];
+        if (npix * 48 > ws.bytes) {
+            if (ws.p) (void)hipFree(ws.p);
+            ws.p = nullptr;
+            ws.bytes = 0;
+            HIP_TRY(hipMalloc(&ws.p, npix * 48));
+            ws.bytes = npix * 48;
+        }
+        planes = (float4 *)ws.p;
+    }
+    float4 *G = planes, *E[2] = {planes + npix, planes + 2 * npix};
+    HIP_TRY(rt_denoise_launch.prepare((uint32_t)npix, color, guides, moments, spp, dp->uniform_spp, dp->demodulate != 0, G,
+                                      E[0], stream));
+    for (int i = 0; i < dp->iterations; i++) {
+        const bool last = i + 1 == dp->iterations;
+        HIP_TRY(rt_denoise_launch.atrous(nx, ny, 1 << i, dp->sigma_color, dp->sigma_depth, moments != nullptr,
+                                         dp->variance_filter, G, E[i & 1], E[(i + 1) & 1], guides, dp->demodulate != 0,
+                                         last ? out : nullptr, stream));
+    }
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_features_dev(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
+                           float *guides_dev, void *stream) {
+    if (int rc = features_check("rt_render_features_dev", s, cam, p, x0, y0, w, h, guides_dev != nullptr)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    return features_run(s, cam, p, x0, y0, w, h, guides_dev, (hipStream_t)stream);
+}
+
+int rt_render_features(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
+                       float *albedo, float *normal, float *depth, float *coverage) {
+    if (int rc = features_check("rt_render_features", s, cam, p, x0, y0, w, h, albedo || normal || depth || coverage))
+        return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t npix = (size_t)w * h, bytes = npix * RT_GUIDE_FLOATS * sizeof(float);
+    if (int rc = s->host_out.reserve(bytes)) return rc;
+    if (int rc = ensure_own_stream(s)) return rc;
+    if (int rc = features_run(s, cam, p, x0, y0, w, h, (float *)s->host_out.p, s->own_stream)) return rc;
+    std::vector<float> g(npix * RT_GUIDE_FLOATS);
+    HIP_TRY(hipMemcpyAsync(g.data(), s->host_out.p, bytes, hipMemcpyDeviceToHost, s->own_stream));
+    HIP_TRY(hipStreamSynchronize(s->own_stream));
+    for (size_t q = 0; q < npix; q++) {
+        const float *v = g.data() + q * RT_GUIDE_FLOATS;
+        if (albedo) { albedo[3 * q] = v[0]; albedo[3 * q + 1] = v[1]; albedo[3 * q + 2] = v[2]; }
+        if (coverage) coverage[q] = v[3];
+        if (normal) { normal[3 * q] = v[4]; normal[3 * q + 1] = v[5]; normal[3 * q + 2] = v[6]; }
+        if (depth) depth[q] = v[7];
+    }
+    return RT_OK;
+}
+
+int rt_denoise_dev(int device, int nx, int ny, const float *color_dev, const float *guides_dev, const float *moments_dev,
+                   const int32_t *spp_dev, const rt_denoise_params *dp, float *out_dev, void *stream) {
+    if (int rc = denoise_check("rt_denoise_dev", nx, ny, !color_dev || !guides_dev || !out_dev, dp, moments_dev != nullptr,
+                               spp_dev != nullptr))
+        return rc;
+    HIP_TRY(hipSetDevice(device));
+    return denoise_run(device, nx, ny, color_dev, guides_dev, moments_dev, spp_dev, dp, out_dev, (hipStream_t)stream);
+}
+
+int rt_denoise(int device, int nx, int ny, const float *color, const float *albedo, const float *normal, const float *depth,
+               const float *moments, const int32_t *spp, const rt_denoise_params *dp, float *out, double *ms) {
+    if (int rc = denoise_check("rt_denoise", nx, ny, !color || !albedo || !normal || !depth || !out, dp, moments != nullptr,
+                               spp != nullptr))
+        return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t npix = (size_t)nx * ny;
+    std::vector<float> g(npix * RT_GUIDE_FLOATS);
+    for (size_t q = 0; q < npix; q++) {   // the packed guides; coverage is not read by the filter
+        float *v = g.data() + q * RT_GUIDE_FLOATS;
+        v[0] = albedo[3 * q]; v[1] = albedo[3 * q + 1]; v[2] = albedo[3 * q + 2]; v[3] = 0.f;
+        v[4] = normal[3 * q]; v[5] = normal[3 * q + 1]; v[6] = normal[3 * q + 2]; v[7] = depth[q];
+    }
+    // one allocation: colour, guides, moments, spp, out
+    const size_t off_g = npix * 3, off_m = off_g + npix * RT_GUIDE_FLOATS, off_s = off_m + npix * 2, off_o = off_s + npix,
+                 total = off_o + npix * 3;
+    float *d = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Guard {
+        float *&d;
+        hipEvent_t *ev;
+        ~Guard() {
+            if (d) (void)hipFree(d);
+            for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+        }
+    } guard{d, ev};
+    HIP_TRY(hipMalloc((void **)&d, total * sizeof(float)));
+    HIP_TRY(hipMemcpy(d, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + off_g, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (moments) HIP_TRY(hipMemcpy(d + off_m, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
+    if (spp) HIP_TRY(hipMemcpy(d + off_s, spp, npix * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipEventCreate(&ev[0]));
+    HIP_TRY(hipEventCreate(&ev[1]));
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
+    if (int rc = denoise_run(device, nx, ny, d, d + off_g, moments ? d + off_m : nullptr,
+                             spp ? (const int32_t *)(d + off_s) : nullptr, dp, d + off_o, nullptr))
+        return rc;
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipMemcpy(out, d + off_o, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (ms) {
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        *ms = (double)t;
+    }
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,550 @@
+// capi_render.cpp — the tile renders of the C ABI: job setup, launch knobs, the megakernel +
+// resolve launches over sample batches, timing and statistics.
+#include <cstdio>
+#include <cstring>
+
+#include "capi_internal.h"
+#include "../hip/rt_moments.h"
+
+namespace {
+
+template <class T>
+int upload(void **dst, const std::vector<T> &v) {
+    *dst = nullptr;
+    if (v.empty()) return RT_OK;
+    HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
+    HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// SURVEY §8d byte model (bytes the algorithm must read or write, independent of
+// this implementation's record padding):
+//   node fetch: the bytes loaded per visit (BVH2 64 B, BVH4 112 B, BVH8 224 B, compressed
+//   BVH8 96 B); sphere 16 B; moving sphere 36 B;
+//   rect 24 B; instance chain entered 32 B; medium record 16 B; material +
+//   texture per shade 16 + 16 B; Perlin turbulence 7 octaves x 8 gradient gathers
+//   x (12 B gradient + 3 x 4 B permutation) = 1344 B; per work item the 4-B job
+//   pixel read and the 16-B partial sum written.  (rt_resolve's own traffic — the
+//   partial sums read back, the output index and the 12-B pixel — is not the
+//   megakernel's.)
+double algorithmic_bytes(const rt_stats &st, double items, int bvh_width) {
+    const double node = bvh_width == 4 ? 112.0 : bvh_width == 8 ? 224.0 : bvh_width == RT_BVH_CW8 ? 96.0 : 64.0;
+    return node * st.node_visits + 16.0 * st.sphere_tests + 36.0 * st.moving_sphere_tests + 24.0 * st.rect_tests +
+           32.0 * st.instanced_tests + 16.0 * st.medium_tests + 32.0 * st.shades + 1344.0 * st.noise_evals +
+           20.0 * items;
+}
+
+// Waves per LDS workgroup that gather the medium cell's paths (rt_kernel.hip stage 6);
+// env RTNW_BALL_WAVES (0: none) for A/B runs.  Their ready batch (RTNW_BALL_BATCH) and the
+// busy lanes below which they claim new samples (RTNW_BALL_CLAIM): 56 and 48 against 48 and
+// 64, c4 48.87 -> 48.50 ms, the share of 8 25.20 -> 25.05 ms (profiles/r06/knobs3_ab.log).
+#define RT_BALL_WAVES 3
+#define RT_BALL_BATCH 56
+#define RT_BALL_CLAIM 48
+// The shading stage's rejection sampler (rt_device.h coop_reject_mixed): candidates each
+// requesting lane tries by itself before the cooperative rounds (RTNW_COOP_LOCAL, 0: none),
+// in waves with at least RTNW_COOP_LOCAL_MIN requesters.  Any setting renders the same image;
+// 2 and 33 against none: c4 48.49 -> 47.21 ms, c3 22.47 -> 21.84, c2 7.85 -> 7.57
+// (profiles/r07/ab_c4.log, ab_c4_sweep.log for the other settings).
+#define RT_COOP_LOCAL 2
+#define RT_COOP_LOCAL_MIN 33
+int ball_waves() {
+    if (const char *e = std::getenv("RTNW_BALL_WAVES")) return std::max(0, std::min(RT_LDS_BLOCK / 64, std::atoi(e)));
+    return RT_BALL_WAVES;
+}
+
+// Small claims per wave at the end of a launch (render_tiles' claim sizes).
+#define RT_TAIL_CLAIMS 32
+
+// Partial-sum slab budget per launch (bytes; env RTNW_SLAB_BUDGET overrides, for tests).
+// A job whose slab would be larger runs as several launches over sample batches.
+// 16 GiB of the 288 GiB HBM: config 5 on one GPU (1e9 samples, 12 GB) is one launch,
+// one launch-end drain; 8 GiB made it two.
+#define RT_SLAB_BUDGET (16ull << 30)
+uint64_t slab_budget() {
+    if (const char *e = std::getenv("RTNW_SLAB_BUDGET")) {
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v > 0) return v;
+    }
+    return RT_SLAB_BUDGET;
+}
+
+void free_job_lists(rt_scene *s) {
+    if (s->job_xy) { (void)hipFree(s->job_xy); s->job_xy = nullptr; }
+    if (s->job_out) { (void)hipFree(s->job_out); s->job_out = nullptr; }
+    s->job_cap = 0;
+}
+
+// Job pixel order: tiles in the order given; inside a tile, bands of 8 rows listed
+// column by column (8 pixels per column), so that ANY 64 consecutive items — a wave
+// claim, wherever it starts — are 8 neighbouring columns of one band (coherent
+// primary rays), also when the tile width is not a multiple of 8 (500 = 62.5 x 8).
+int prepare_job(rt_scene *s, const int32_t *tiles, int ntiles, int nx, int ny, const rt_camera_desc *cam) {
+    std::vector<int32_t> key(tiles, tiles + 4 * ntiles);
+    // the deep-first order depends on the camera: its rays' frame joins the cache key
+    const bool deep = deep_first(s);
+    key.push_back(nx);
+    key.push_back(ny);
+    key.push_back(deep ? 1 : 0);
+    if (deep) {
+        const float *cf[4] = {cam->origin, cam->lower_left_corner, cam->horizontal, cam->vertical};
+        for (const float *f : cf)
+            for (int k = 0; k < 3; k++) { int32_t b; std::memcpy(&b, &f[k], 4); key.push_back(b); }
+    }
+    if (key == s->job_tiles && s->job_xy) return RT_OK;
+    std::vector<uint32_t> xy, oi;
+    uint32_t base = 0;
+    for (int t = 0; t < ntiles; t++) {
+        const int x0 = tiles[4 * t], y0 = tiles[4 * t + 1], w = tiles[4 * t + 2], h = tiles[4 * t + 3];
+        if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 + w > nx || y0 + h > ny || nx > 65535 || ny > 65535)
+            return fail(RT_ERR_INVALID, "tile outside the image");
+        for (int by = 0; by < h; by += 8)
+            for (int xx = 0; xx < w; xx++)
+                for (int yy = by; yy < std::min(by + 8, h); yy++) {
+                    xy.push_back((uint32_t)(x0 + xx) | ((uint32_t)(y0 + yy) << 16));
+                    oi.push_back(base + (uint32_t)(yy * w + xx));
+                }
+        base += (uint32_t)(w * h);
+    }
+    // deep pixels first, each group in the band order above (a claim of 64 consecutive
+    // items stays 64 neighbouring pixels of one group)
+    uint32_t ndeep = 0;
+    if (deep) {
+        std::vector<uint32_t> dxy, doi, rxy, roi;
+        for (size_t i = 0; i < xy.size(); i++) {
+            const bool in = deep_pixel(s, cam, (int)(xy[i] & 0xFFFFu), (int)(xy[i] >> 16), nx, ny);
+            (in ? dxy : rxy).push_back(xy[i]);
+            (in ? doi : roi).push_back(oi[i]);
+        }
+        ndeep = (uint32_t)dxy.size();
+        if (ndeep == xy.size()) ndeep = 0;   // all deep: one group
+        dxy.insert(dxy.end(), rxy.begin(), rxy.end());
+        doi.insert(doi.end(), roi.begin(), roi.end());
+        xy.swap(dxy);
+        oi.swap(doi);
+    }
+    free_job_lists(s);
+    s->job_tiles.clear();
+    if (int rc = upload(&s->job_xy, xy)) return rc;
+    if (int rc = upload(&s->job_out, oi)) return rc;
+    s->job_cap = xy.size();
+    s->npix = (uint32_t)xy.size();
+    s->job_ndeep = ndeep;
+    s->job_tiles = key;
+    return RT_OK;
+}
+
+// A job over any subset of a frame with explicit output slots (rt_render_adaptive's later
+// passes): job pixel k is image pixel xy[k] (x | y << 16) and reads and writes its sums and
+// moments at slot[k] of the caller's full-frame buffers, in place — no gather or scatter
+// copies.  The pixels are claimed in the order given; the caller lists the deep ones first
+// (ndeep of them: a frame's deep pixels are found once, not per pass).  xy and slot are
+// pinned host memory that stays as it is until the job's launches have completed: they are
+// copied on the job's stream, over the previous job's lists when those have the room (the
+// caller has waited for the launches that read them).  Such a job never answers a later
+// tile job's cache lookup: it leaves no key behind.
+int prepare_job_slots(rt_scene *s, const JobSlots &js, int nx, int ny, hipStream_t stream) {
+    if (js.n == 0 || js.ndeep > js.n || nx > 65535 || ny > 65535) return fail(RT_ERR_INVALID, "empty job or image too large");
+    for (uint32_t i = 0; i < js.n; i++)
+        if ((int)(js.xy[i] & 0xFFFFu) >= nx || (int)(js.xy[i] >> 16) >= ny) return fail(RT_ERR_INVALID, "job pixel outside the image");
+    s->job_tiles.clear();
+    if (!s->job_xy || !s->job_out || js.n > s->job_cap) {
+        free_job_lists(s);
+        HIP_TRY(hipMalloc(&s->job_xy, (size_t)js.n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&s->job_out, (size_t)js.n * sizeof(uint32_t)));
+        s->job_cap = js.n;
+    }
+    HIP_TRY(hipMemcpyAsync(s->job_xy, js.xy, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(s->job_out, js.slot, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    s->npix = js.n;
+    s->job_ndeep = js.ndeep == js.n ? 0 : js.ndeep;   // all deep: one group
+    return RT_OK;
+}
+
+// The counters of a RT_FLAG_COUNT or RT_FLAG_PROFILE render, read back into `stats`.
+int read_counters(rt_scene *s, bool count, bool prof, double items, rt_stats *stats) {
+    if (count) {
+        unsigned long long c[RT_CNT_N];
+        HIP_TRY(hipMemcpy(c, s->stats, sizeof c, hipMemcpyDeviceToHost));
+        stats->samples = (double)c[RT_CNT_SAMPLES];
+        stats->segments = (double)c[RT_CNT_SEGMENTS];
+        stats->node_visits = (double)c[RT_CNT_NODES];
+        stats->sphere_tests = (double)c[RT_CNT_SPHERES];
+        stats->moving_sphere_tests = (double)c[RT_CNT_MSPHERES];
+        stats->rect_tests = (double)c[RT_CNT_RECTS];
+        stats->instanced_tests = (double)c[RT_CNT_INSTANCED];
+        stats->medium_tests = (double)c[RT_CNT_MEDIA];
+        stats->shades = (double)c[RT_CNT_SHADES];
+        stats->noise_evals = (double)c[RT_CNT_NOISE];
+        stats->algorithmic_bytes = algorithmic_bytes(*stats, items, s->bvh_width);
+        unsigned long long w[5];
+        HIP_TRY(hipMemcpy(w, (unsigned long long *)s->stats + RT_STAT_WAVE, sizeof w, hipMemcpyDeviceToHost));
+        stats->wave_iterations = (double)w[0];
+        stats->wave_node_trips = (double)w[1];
+        stats->wave_prim_trips = (double)w[2];
+        stats->wave_sphere_draw_trips = (double)w[3];
+        stats->lane_sphere_draw_trips = (double)w[4];
+        unsigned long long sh[3];
+        HIP_TRY(hipMemcpy(sh, (unsigned long long *)s->stats + RT_STAT_SHADE, sizeof sh, hipMemcpyDeviceToHost));
+        stats->wave_shade_passes = (double)sh[0];
+        stats->wave_shade_kinds = (double)sh[1];
+        stats->lane_scatters = (double)sh[2];
+        if (std::getenv("RTNW_TRACE")) {   // the ball waves (rt_kernel.hip stage 6), diagnostics only
+            unsigned long long b[RT_BALL_N];
+            HIP_TRY(hipMemcpy(b, (unsigned long long *)s->stats + RT_STAT_BALL, sizeof b, hipMemcpyDeviceToHost));
+            std::fprintf(stderr,
+                         "rtnw ball waves: iterations %llu, live lanes / iteration %.1f, traversal rounds / iteration %.2f, "
+                         "cell-decided segments in ball waves %llu, pushes refused (pool full) %llu (of %.0f segments), pushed in %llu, "
+                         "pushed out %llu, taken %llu\n",
+                         b[RT_BALL_ITERS], b[RT_BALL_ITERS] ? (double)b[RT_BALL_LIVE] / b[RT_BALL_ITERS] : 0.0,
+                         b[RT_BALL_ITERS] ? (double)b[RT_BALL_ROUNDS] / b[RT_BALL_ITERS] : 0.0, b[RT_BALL_CELL_BALL],
+                         b[RT_BALL_DENIED], stats->segments, b[RT_BALL_PUSH_IN], b[RT_BALL_PUSH_OUT], b[RT_BALL_TAKEN]);
+            unsigned long long r[RT_SAMPLER_N];
+            HIP_TRY(hipMemcpy(r, (unsigned long long *)s->stats + RT_STAT_SAMPLER, sizeof r, hipMemcpyDeviceToHost));
+            std::fprintf(stderr,
+                         "rtnw shading-stage sampler: local trips / iteration %.3f, cooperative rounds / iteration %.3f; "
+                         "ball waves: %.3f and %.3f\n",
+                         w[0] ? (double)r[RT_SAMPLER_LOCAL] / w[0] : 0.0, w[0] ? (double)r[RT_SAMPLER_ROUNDS] / w[0] : 0.0,
+                         b[RT_BALL_ITERS] ? (double)r[RT_SAMPLER_BALL_LOCAL] / b[RT_BALL_ITERS] : 0.0,
+                         b[RT_BALL_ITERS] ? (double)r[RT_SAMPLER_BALL_ROUNDS] / b[RT_BALL_ITERS] : 0.0);
+        }
+    }
+    if (prof) {
+        unsigned long long c[RT_STATS_LEN];
+        HIP_TRY(hipMemcpy(c, s->stats, sizeof c, hipMemcpyDeviceToHost));
+        if (std::getenv("RTNW_TRACE")) {   // the ball waves' share of the stage cycles (diagnostics only)
+            const unsigned long long *b = c + RT_STAT_BALL;
+            std::fprintf(stderr,
+                         "rtnw ball waves (profile): iterations %llu of %llu; cycles claim %llu of %llu, traverse %llu of "
+                         "%llu, media %llu of %llu, shade %llu of %llu\n",
+                         b[4], b[5], b[0], c[RT_STAT_PROF], b[1], c[RT_STAT_PROF + 1], b[2], c[RT_STAT_PROF + 2], b[3],
+                         c[RT_STAT_PROF + 3]);
+        }
+        stats->cycles_claim = (double)c[RT_STAT_PROF + 0];
+        stats->cycles_traverse = (double)c[RT_STAT_PROF + 1];
+        stats->cycles_media = (double)c[RT_STAT_PROF + 2];
+        stats->cycles_shade = (double)c[RT_STAT_PROF + 3];
+        stats->cycles_scatter = (double)c[RT_STAT_SHADE + 3];
+        // wave timeline of the last batch, s_memrealtime at 100 MHz (kernel: kProf)
+        const unsigned long long *T = c + RT_STAT_TIME;
+        const double t0 = (double)~T[0], us = 0.01;
+        stats->wave_exhaust_first_us = ((double)~T[1] - t0) * us;
+        stats->wave_exhaust_last_us = ((double)T[2] - t0) * us;
+        stats->wave_end_first_us = ((double)~T[3] - t0) * us;
+        stats->wave_end_last_us = ((double)T[4] - t0) * us;
+        stats->wave_end_mean_us = T[6] ? (double)T[5] / (double)T[6] * us : 0.0;   // T[5]: sum of lifetimes
+    }
+    return RT_OK;
+}
+
+}  // namespace
+
+// The scene part of a launch's arguments: the arrays, and what rt_scene_create found.
+void fill_scene_args(const rt_scene *s, RtKernelArgs &a) {
+    a.nodes = (const float4 *)s->nodes;
+    a.prims = (const float4 *)s->prims;
+    a.bprims = (const float4 *)s->bprims;
+    a.media = (const int4 *)s->media;
+    a.mats = (const float4 *)s->mats;
+    a.texs = (const float4 *)s->texs;
+    a.insts = (const float4 *)s->insts;
+    a.ranvec = (const float4 *)s->ranvec;
+    a.perm = (const int *)s->perm;
+    a.texels = (const uint8_t *)s->texels;
+    a.root = s->root;
+    a.nnodes = (uint32_t)s->nnodes;
+    a.bvh_width = s->bvh_width;
+    a.has_bvh = s->has_bvh;
+    a.nmedia = s->nmedia;
+    a.lds_nodes = s->lds_nodes ? 1 : 0;
+    a.scan = s->scan ? 1 : 0;
+    a.groups = (const float4 *)s->groups;
+    a.ngroups = s->ngroups;
+    a.nprescan = s->nprescan;
+    a.cell_first = s->cell_first;
+    a.cell_n = s->cell_n;
+    for (int k = 0; k < 3; k++) a.cell_c[k] = s->cell_c[k];
+    a.cell_r2 = s->cell_r2;
+    a.cell_rin2 = s->cell_rin2;
+    a.nprims = (uint32_t)s->nprims;
+    a.stack_depth = s->stack_depth;
+    a.features = scene_features(s);
+}
+
+// The camera and the image part: what a primary ray is made from.
+void fill_camera_args(const rt_camera_desc *cam, const rt_render_params *p, RtKernelArgs &a) {
+    for (int k = 0; k < 3; k++) {
+        a.org[k] = cam->origin[k];
+        a.llc[k] = cam->lower_left_corner[k];
+        a.hor[k] = cam->horizontal[k];
+        a.ver[k] = cam->vertical[k];
+        a.cu[k] = cam->u[k];
+        a.cv[k] = cam->v[k];
+    }
+    a.lens = cam->lens_radius;
+    a.ct0 = cam->time0;
+    a.ct1 = cam->time1;
+    a.nx = p->nx;
+    a.ny = p->ny;
+    a.rnx = 1.0f / (float)p->nx;   // nx, ny >= 1: normal reciprocals (div_rn, rt_device.h)
+    a.rny = 1.0f / (float)p->ny;
+    a.tmin = p->t_min;
+    a.seed = p->seed;
+}
+
+// Whether a job lists the pixels whose primary rays enter a dense medium first
+// (RTNW_DEEP_FIRST=0: never).
+bool deep_first(const rt_scene *s) {
+    bool v = !s->deep_balls.empty();
+    if (const char *e = std::getenv("RTNW_DEEP_FIRST")) v = v && std::atoi(e) != 0;
+    return v;
+}
+
+bool deep_pixel(const rt_scene *s, const rt_camera_desc *cam, int x, int y, int nx, int ny) {
+    // the pixel centre's primary ray (main.cpp:305-306, camera.h:52-55 without jitter or lens)
+    const float u = (x + 0.5f) / nx, v = (ny - 1 - y + 0.5f) / ny;
+    float o[3], d[3];
+    for (int k = 0; k < 3; k++) {
+        o[k] = cam->origin[k];
+        d[k] = cam->lower_left_corner[k] + u * cam->horizontal[k] + v * cam->vertical[k] - o[k];
+    }
+    for (size_t b = 0; b + 3 < s->deep_balls.size(); b += 4) {
+        const float *c = &s->deep_balls[b];
+        const double oc[3] = {o[0] - (double)c[0], o[1] - (double)c[1], o[2] - (double)c[2]};
+        const double a = (double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2];
+        const double bb = oc[0] * d[0] + oc[1] * d[1] + oc[2] * d[2];
+        const double cc = oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2] - (double)c[3] * c[3];
+        if (bb * bb - a * cc > 0 && (bb < 0 || cc < 0)) return true;
+    }
+    return false;
+}
+
+// The body of rt_render_tiles and rt_render_tiles_moments: the job is the tile list, or `js`
+// when non-null; with mom_dev the resolve is rt_moments.hip's, which also keeps the moments.
+int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
+               const JobSlots *js, float *out_dev, float *mom_dev, void *stream_v, rt_stats *stats) {
+    if (p->nx <= 0 || p->ny <= 0 || p->spp <= 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "bad render parameters");
+    if (s->has_moving && (cam->time0 < s->time0 || cam->time1 > s->time1))
+        return fail(RT_ERR_INVALID, "camera shutter outside the scene's time span (moving-sphere bounds)");
+    // RT_FLAG_RIGHT_FOLD (rt_hip.h): plain renders of width-2 scenes only, and a stack of
+    // max_depth attenuations (16 B each) for every lane of the launch, within the slab
+    // budget's default (RTNW_SLAB_BUDGET shapes the sample batches, not this bound)
+    const bool fold = (p->flags & RT_FLAG_RIGHT_FOLD) != 0;
+    const uint64_t fold_lanes = (uint64_t)s->grid[0] * (s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK);
+    const uint64_t fold_bytes = fold ? fold_lanes * (uint64_t)std::max(1, p->max_depth) * sizeof(float4) : 0;
+    if (fold) {
+        if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE))
+            return fail(RT_ERR_INVALID, "RT_FLAG_RIGHT_FOLD cannot be combined with RT_FLAG_COUNT or RT_FLAG_PROFILE");
+        if (s->bvh_width != 2)
+            return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_RIGHT_FOLD needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
+        if (!rt_megakernel_has_fold())
+            return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_RIGHT_FOLD: this library was linked without the fold variants (rt_kernel_fold.o)");
+        if (fold_bytes > RT_SLAB_BUDGET)
+            return fail(RT_ERR_INVALID, "RT_FLAG_RIGHT_FOLD: max_depth " + std::to_string(p->max_depth) + " needs a " +
+                                            std::to_string(fold_bytes) + "-byte attenuation stack, over the " +
+                                            std::to_string(RT_SLAB_BUDGET) + "-byte budget");
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (int rc = js ? prepare_job_slots(s, *js, p->nx, p->ny, stream) : prepare_job(s, tiles, ntiles, p->nx, p->ny, cam))
+        return rc;
+
+    // Work item = `chunk` samples of one pixel, one by default: short items keep each
+    // wave's lanes on neighbouring pixels (a wave deals its claims to lanes as they free
+    // up; long items let its pixels drift apart): 16 -> 1 sample per item is 92.2 ->
+    // 81.8 ms on c4.  The partial-sum slab holds one rgb (12 B) per item
+    // of a launch; a job whose slab would pass the budget runs as several launches
+    // over sample batches (whole chunks), and the resolve adds every batch to a
+    // per-pixel running sum in sample order — so the sum is the same sequence of
+    // float adds whatever the batch size, i.e. the image does not depend on the job's
+    // size (one GPU or a rank's share of eight).
+    const int chunk = p->chunk > 0 ? p->chunk : 1;
+    const uint64_t nchunks_total = ((uint64_t)p->spp + chunk - 1) / chunk;
+    const uint64_t max_items = 0xFFFFFFFFull - 64;
+    if ((uint64_t)s->npix > max_items) return fail(RT_ERR_INVALID, "job too large (pixels >= 2^32)");
+    const uint64_t item_bytes = 4 * (uint64_t)rt_slab_floats();   // one partial sum (rgb)
+    uint64_t per = std::max<uint64_t>(1, slab_budget() / ((uint64_t)s->npix * item_bytes));
+    per = std::min<uint64_t>(per, max_items / s->npix);
+    per = std::min<uint64_t>(per, nchunks_total);
+    const uint64_t nbatches = (nchunks_total + per - 1) / per;
+    per = (nchunks_total + nbatches - 1) / nbatches;   // batches of (nearly) equal size, as many
+    if (int rc = s->slab.reserve((size_t)s->npix * per * item_bytes)) return rc;
+    if (int rc = s->acc.reserve(nbatches > 1 ? (size_t)s->npix * 16 : 0)) return rc;
+    if (int rc = s->fold.reserve(fold_bytes)) return rc;
+    const bool count = (p->flags & RT_FLAG_COUNT) != 0;
+    const bool prof = !count && (p->flags & RT_FLAG_PROFILE) != 0;
+    const bool sum_in = (p->flags & RT_FLAG_SUM_IN) != 0, sum_out = (p->flags & RT_FLAG_SUM_OUT) != 0;
+    const int mode = count ? 1 : (prof ? 2 : 0);
+    if (count || prof) HIP_TRY(hipMemsetAsync(s->stats, 0, RT_STATS_LEN * sizeof(unsigned long long), stream));
+
+    RtKernelArgs a{};
+    fill_scene_args(s, a);
+    fill_camera_args(cam, p, a);
+    a.need_dlen = s->nmedia > 0 || s->has_specular || p->background == RT_BG_SKY;
+    a.ball_waves = ball_waves();
+    a.ball_batch = env_int("RTNW_BALL_BATCH", RT_BALL_BATCH, 1, 64);
+    a.ball_claim = env_int("RTNW_BALL_CLAIM", RT_BALL_CLAIM, 1, 64);
+    a.ball_park = env_int("RTNW_BALL_PARK", 1, 0, 1);
+    a.ball_drain = env_int("RTNW_BALL_DRAIN", 1, 0, 1);
+    a.coop_local = env_int("RTNW_COOP_LOCAL", RT_COOP_LOCAL, 0, 3);
+    a.coop_local_min = env_int("RTNW_COOP_LOCAL_MIN", RT_COOP_LOCAL_MIN, 1, 64);
+    a.ns = p->spp;
+    a.max_depth = p->max_depth;
+    a.background = p->background;
+    a.chunk = chunk;
+    a.job_xy = (const uint32_t *)s->job_xy;
+    a.npix = s->npix;
+    a.slab = (float *)s->slab.p;
+    a.counter = (uint32_t *)s->counter;
+    a.stats = (unsigned long long *)s->stats;
+    // RTNW_WAVE_LOG=<file> with RT_FLAG_PROFILE: every wave's timeline appended to the
+    // file as 5 uint64 (start, pool dry, end in s_memrealtime ticks, xcc << 32 | HW_ID,
+    // items claimed) per wave and batch (tools/tail_probe.py --wave-log; diagnostics)
+    const char *wave_log_path = prof ? std::getenv("RTNW_WAVE_LOG") : nullptr;
+    unsigned long long *wave_log = nullptr;
+    struct FreeOnExit {   // every return below, error paths included, frees the log buffer
+        unsigned long long *&p;
+        ~FreeOnExit() { if (p) (void)hipFree(p); }
+    } wave_log_guard{wave_log};
+    const size_t wave_log_n = (size_t)s->grid[2] * ((s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK) / 64) * RT_WAVE_LOG_WORDS;
+    if (wave_log_path) {
+        HIP_TRY(hipMalloc(&wave_log, wave_log_n * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(wave_log, 0, wave_log_n * sizeof(unsigned long long), stream));
+    }
+    a.wave_log = wave_log;
+    a.fold = fold ? (float4 *)s->fold.p : nullptr;
+    a.fold_stride = (uint32_t)fold_lanes;
+
+    // vec3::operator/= (vec3.h:134-141): col *= float(1.0 / ns)
+    const uint32_t ns_total = sum_in ? p->sample_offset + (uint32_t)p->spp : (uint32_t)p->spp;
+    const float k = (float)(1.0 / (double)(float)ns_total);
+    const uint64_t waves = (uint64_t)s->grid[mode] * ((s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK) / 64);
+    double kernel_ms = 0, resolve_ms = 0;
+    for (uint64_t b = 0; b < nbatches; ++b) {
+        const uint64_t c0 = b * per, c1 = std::min(c0 + per, nchunks_total);
+        const uint64_t s0 = c0 * (uint64_t)chunk, s1 = std::min<uint64_t>(c1 * (uint64_t)chunk, (uint64_t)p->spp);
+        a.ns = (int)(s1 - s0);                                   // samples of this batch
+        a.sample_offset = p->sample_offset + (uint32_t)s0;       // their first sample index
+        a.nchunks = (int)(c1 - c0);
+        const uint64_t nitems = (uint64_t)s->npix * (c1 - c0);
+        a.nitems = (uint32_t)nitems;
+        a.ndeep = s->job_ndeep;
+        a.ndeep_items = (uint32_t)((uint64_t)s->job_ndeep * (c1 - c0));
+        // Claim size: up to 512 items per atomic (64 -> 512 is 81.6 -> 76.9 ms on c4:
+        // fewer round trips to the one contended counter), at least 8
+        // claims per wave so that small jobs still spread over every wave.
+        // The last RT_TAIL_CLAIMS claims per wave are of 64 items: with 512-item claims
+        // to the end, the waves ran dry over 2.4 ms (the first found the pool empty at
+        // 54.1 ms of a 57.1-ms launch, the last at 56.5; with 64-item claims over 0.5 ms,
+        // but every claim is a round trip to the one device-scope counter:
+        // tools/tail_probe.py).
+        {
+            uint64_t c = std::min<uint64_t>(std::max<uint64_t>(nitems / (waves * 8) / 64 * 64, 64), 512);
+            uint64_t tail = 64 * RT_TAIL_CLAIMS * waves;
+            if (const char *e = std::getenv("RTNW_CLAIM")) c = (uint64_t)std::max(1, std::atoi(e)) * 64;   // x 64 items
+            if (const char *e = std::getenv("RTNW_TAIL_CLAIMS")) tail = 64 * (uint64_t)std::max(0, std::atoi(e)) * waves;
+            a.claim = (uint32_t)c;
+            a.claim_tail = 64;
+            a.nbig = (uint32_t)(nitems > tail ? (nitems - tail) / c : 0);
+        }
+        const int rmode = (b == 0 ? RT_RESOLVE_FIRST : 0) | (b + 1 == nbatches ? RT_RESOLVE_LAST : 0) |
+                          (sum_in ? RT_RESOLVE_SUM_IN : 0) | (sum_out ? RT_RESOLVE_RAW : 0);
+        HIP_TRY(hipMemsetAsync(s->counter, 0, 64, stream));
+        // the wave timeline describes the last batch: its slots start from zero each launch
+        if (prof)
+            HIP_TRY(hipMemsetAsync((unsigned long long *)s->stats + RT_STAT_TIME, 0, 7 * sizeof(unsigned long long), stream));
+        HIP_TRY(hipEventRecord(s->ev[0], stream));
+        HIP_TRY(rt_launch_megakernel(&a, s->grid[mode], fold ? RT_LAUNCH_FOLD : mode, stream));
+        HIP_TRY(hipEventRecord(s->ev[1], stream));
+        if (mom_dev)
+            HIP_TRY(rt_moments_launch.resolve((const float *)s->slab.p, rt_slab_floats(), s->npix, a.nchunks, k,
+                                             (float4 *)s->acc.p, rmode, (const uint32_t *)s->job_out, out_dev, mom_dev,
+                                             stream));
+        else
+            HIP_TRY(rt_launch_resolve((const float *)s->slab.p, s->npix, a.nchunks, k, (float4 *)s->acc.p, rmode,
+                                      (const uint32_t *)s->job_out, out_dev, stream));
+        HIP_TRY(hipEventRecord(s->ev[2], stream));
+        if (wave_log) {
+            std::vector<unsigned long long> h(wave_log_n);   // the render stream may be non-blocking
+            HIP_TRY(hipMemcpyAsync(h.data(), wave_log, h.size() * sizeof h[0], hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (FILE *f = std::fopen(wave_log_path, "ab")) {
+                std::fwrite(h.data(), sizeof h[0], h.size(), f);
+                std::fclose(f);
+            }
+        }
+        if (stats) {   // one batch at a time: the events are reused
+            HIP_TRY(hipEventSynchronize(s->ev[2]));
+            float ms0 = 0, ms1 = 0;
+            HIP_TRY(hipEventElapsedTime(&ms0, s->ev[0], s->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms1, s->ev[1], s->ev[2]));
+            kernel_ms += ms0;
+            resolve_ms += ms1;
+        }
+    }
+
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->samples = (double)s->npix * (double)p->spp;
+        stats->chunk = (double)chunk;
+        stats->batches = (double)nbatches;
+        stats->kernel_ms = kernel_ms;
+        stats->resolve_ms = resolve_ms;
+        if (int rc = read_counters(s, count, prof, (double)s->npix * (double)nchunks_total, stats)) return rc;
+        stats->grid = (double)s->grid[mode];
+        stats->lds_level = s->lds_nodes ? 1.0 : 0.0;
+        stats->scan_groups = s->scan ? (double)s->ngroups : 0.0;
+        stats->prescan = (double)s->nprescan;
+        stats->stack_depth = (double)(s->lds_nodes ? s->stack_depth : s->bvh_width >= 8 ? RT_STACK_DEPTH_W8 : RT_STACK_DEPTH);
+    }
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
+                    float *out_dev, void *stream_v, rt_stats *stats) {
+    if (!s || !cam || !p || ntiles < 0) return fail(RT_ERR_INVALID, "rt_render_tiles: bad argument");
+    if (ntiles == 0) {   // a rank with no tiles (more ranks than tiles) has nothing to do
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    if (!tiles || !out_dev) return fail(RT_ERR_INVALID, "rt_render_tiles: null tiles or output");
+    return render_job(s, cam, p, tiles, ntiles, nullptr, out_dev, nullptr, stream_v, stats);
+}
+
+int rt_render_tiles_moments(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles,
+                            int ntiles, float *out_dev, float *moments_dev, void *stream_v, rt_stats *stats) {
+    if (!cam || !p || ntiles < 0) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: bad argument");
+    if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE))
+        return fail(RT_ERR_INVALID, "rt_render_tiles_moments: RT_FLAG_COUNT and RT_FLAG_PROFILE are not supported");
+    if (!s) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: null scene");
+    if (!rt_moments_launch.resolve)
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_tiles_moments: this library was linked without the moments unit (rt_moments.o)");
+    if (ntiles == 0) {
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RT_OK;
+    }
+    if (!tiles || !out_dev || !moments_dev) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: null tiles, output or moments");
+    return render_job(s, cam, p, tiles, ntiles, nullptr, out_dev, moments_dev, stream_v, stats);
+}
+
+int rt_render_tile(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
+                   float *out_rgb, rt_stats *stats) {
+    if (!s || !out_rgb) return fail(RT_ERR_INVALID, "rt_render_tile: bad argument");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)w * h * 3 * sizeof(float);
+    if (w <= 0 || h <= 0) return fail(RT_ERR_INVALID, "empty tile");
+    if (int rc = s->host_out.reserve(bytes)) return rc;
+    if (int rc = ensure_own_stream(s)) return rc;
+    const int32_t tile[4] = {x0, y0, w, h};
+    if (p && (p->flags & RT_FLAG_SUM_IN))   // the running sums come from the caller's buffer
+        HIP_TRY(hipMemcpyAsync(s->host_out.p, out_rgb, bytes, hipMemcpyHostToDevice, s->own_stream));
+    rt_stats local;
+    if (int rc = rt_render_tiles(s, cam, p, tile, 1, (float *)s->host_out.p, s->own_stream, stats ? stats : &local)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_rgb, s->host_out.p, bytes, hipMemcpyDeviceToHost, s->own_stream));
+    HIP_TRY(hipStreamSynchronize(s->own_stream));
+    return RT_OK;
+}
+
+}  // extern "C"

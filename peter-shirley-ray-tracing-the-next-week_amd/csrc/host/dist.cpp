@@ -17,7 +17,7 @@
 
 #include "rt_hip.h"
 
-// error plumbing shared with capi.cpp (thread-local message)
+// error plumbing shared with capi_util.cpp (thread-local message)
 int rt_internal_fail(int code, const std::string &msg);
 
 namespace {

@@ -1,5 +1,5 @@
 // rt_layout.h — the scene's layout in HBM, shared by the host uploader
-// (capi.cpp) and the megakernel (rt_kernel.hip).
+// (scene_lower.cpp) and the megakernel (rt_kernel.hip).
 //
 // Everything the traversal touches is a 16-byte-aligned record read with
 // dwordx4 loads: an incoherent wave fetches one whole record per lane per
@@ -94,7 +94,7 @@ struct rt_dprim {
     float g1[4], g2[4];
 };
 
-// Flat scan (scenes of at most RT_SCAN_MAX surface primitives, capi.cpp): the
+// Flat scan (scenes of at most RT_SCAN_MAX surface primitives, scene_lower.cpp): the
 // primitives are ordered by instance chain, and each run of one chain is a group,
 // 48 B: (first, count, instance (-1 none), kinds) + its world box as in a BVH node,
 // (lo.x, hi.x, lo.y, hi.y), (lo.z, hi.z, n_yz, -).  Within a group the primitives
@@ -105,9 +105,9 @@ struct rt_dprim {
 // loop per kind: the instance level of a two-level structure, without per-leaf
 // transforms or per-primitive kind branches.
 #define RT_SCAN_MAX 64
-// BVH scenes: at most this many of the largest primitives are pre-scanned (capi.cpp).
+// BVH scenes: at most this many of the largest primitives are pre-scanned (scene_lower.cpp).
 #define RT_PRESCAN_MAX 8
-// The medium cell: at most this many primitives near a dense medium's ball (capi.cpp).
+// The medium cell: at most this many primitives near a dense medium's ball (scene_lower.cpp).
 #define RT_CELL_MAX 4
 struct rt_dgroup {
     int32_t first, count, instance, kinds;
@@ -116,9 +116,9 @@ struct rt_dgroup {
 };
 
 // Material, 32 B: (kind, texture, fuzz, ref_idx) + (albedo.xyz, flags).  A dielectric
-// carries (float)(1.0/(double)ref_idx), schlick r0^2 and ref_idx^2 in albedo (capi.cpp).
+// carries (float)(1.0/(double)ref_idx), schlick r0^2 and ref_idx^2 in albedo (scene_lower.cpp).
 // flags: 1 a texture of the material reads (u, v); 2 its texture is a constant whose
-// color is in albedo (textured kinds only: capi.cpp)
+// color is in albedo (textured kinds only: scene_lower.cpp)
 struct rt_dmaterial {
     int32_t kind, texture;
     float fuzz, ref_idx;

@@ -1,6 +1,7 @@
 // tests/native/host_sanitize.cpp — drives the host side of librt_hip.so (scene
 // builders, flattening, every BVH form, the PNG decoder, the C ABI's host-only
-// helpers and its error paths) in a build whose host objects carry
+// helpers and its error paths, and the lowering of every built-in scene to the image of the
+// device's arrays, whose invariants are checked here) in a build whose host objects carry
 // AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_sanitizers.py; the
 // device code object is linked in unsanitised, as the GPU sanitizer is not
 // available).  Exit 0 = every call returned as expected and no sanitizer fired.
@@ -16,8 +17,10 @@
 #include <unistd.h>
 
 #include "rt_hip.h"
+#include "../rt_layout.h"
 #include "bvh.h"
 #include "rtnw.h"
+#include "scene_lower.h"
 
 namespace {
 
@@ -29,6 +32,78 @@ int failures = 0;
             failures++;                                                    \
         }                                                                  \
     } while (0)
+
+// rtnw::lower_scene under the knobs set by the caller: what the kernel relies on in the image.
+void lowering(const char *name, const rt_scene_desc *d) {
+    const int before = failures;
+    rtnw::LoweredScene L;
+    EXPECT(rtnw::validate_desc(d) == RT_OK);
+    EXPECT(rtnw::lower_scene(d, &L) == RT_OK);
+    if (L.image.empty()) { EXPECT(!"empty image"); return; }
+    const size_t node_bytes = L.bvh_width == 4 ? sizeof(rt_dnode4) : L.bvh_width == 8 ? sizeof(rt_dnode8)
+                            : L.bvh_width == RT_BVH_CW8 ? sizeof(rt_dnode8q) : sizeof(rt_dnode2);
+    const size_t nstaged = (size_t)L.nprims + (L.scan ? 0 : (size_t)L.cell_n);
+    // the arrays in the order they are staged: offset, bytes (0: empty, a sentinel)
+    const struct { const char *what; size_t off, bytes; } arr[] = {
+        {"nodes", L.nodes, (size_t)L.nnodes * node_bytes},
+        {"prims", L.prims, nstaged * sizeof(rt_dprim)},
+        {"bprims", L.bprims, (size_t)d->nboundary * sizeof(rt_dprim)},
+        {"media", L.media, (size_t)d->nmedia * sizeof(rt_dmedium)},
+        {"mats", L.mats, (size_t)d->nmaterials * sizeof(rt_dmaterial)},
+        {"texs", L.texs, (size_t)d->ntextures * sizeof(rt_dtexture)},
+        {"insts", L.insts, (size_t)d->ninstances * sizeof(rt_dinstance)},
+        {"groups", L.groups, (size_t)L.ngroups * sizeof(rt_dgroup)},
+        {"ranvec", L.ranvec, 256 * 4 * sizeof(float)},
+        {"perm", L.perm, 768 * sizeof(int32_t)},
+        {"texels", L.texels, d->nimages > 0 ? (size_t)d->image_bytes : 0},
+    };
+    const size_t n = sizeof arr / sizeof arr[0];
+    int sentinels = 0;
+    for (size_t i = 0; i < n; i++) {
+        // 256-B aligned, inside the image, and up to the next array (the image's end for the last)
+        const size_t end = i + 1 < n ? arr[i + 1].off : L.image.size(), bytes = arr[i].bytes ? arr[i].bytes : 256;
+        EXPECT(arr[i].off % 256 == 0 && arr[i].off < L.image.size());
+        EXPECT(arr[i].off + bytes <= end && end <= L.image.size());
+        EXPECT(i + 1 == n ? end == arr[i].off + bytes : end == ((arr[i].off + bytes + 255) & ~(size_t)255));
+        if (failures != before) { std::printf("  (%s: %s)\n", name, arr[i].what); return; }
+        if (arr[i].bytes) continue;
+        sentinels++;   // an empty array: one zeroed 256-B block
+        for (size_t b = 0; b < 256; b++) EXPECT(L.image[arr[i].off + b] == 0);
+    }
+    EXPECT(L.nprims == d->nprims && L.has_bvh == (d->nprims > 0));
+    // the order words over [0, nprims): a permutation of the input indices, the pre-scanned first, ascending
+    std::vector<rt_dprim> prims(nstaged);
+    if (nstaged) std::memcpy(prims.data(), L.image.data() + L.prims, nstaged * sizeof(rt_dprim));
+    std::vector<char> seen(L.nprims, 0);
+    for (int i = 0; i < L.nprims; i++) {
+        const int o = prims[i].m[3];
+        EXPECT(o >= 0 && o < L.nprims && !seen[o]);
+        if (o >= 0 && o < L.nprims) seen[o] = 1;
+    }
+    EXPECT(L.nprescan >= 0 && L.nprescan <= RT_PRESCAN_MAX && L.nprescan <= L.nprims);
+    for (int i = 1; i < L.nprescan && i < L.nprims; i++) EXPECT(prims[i - 1].m[3] < prims[i].m[3]);
+    // the medium cell's copies follow, each naming an input primitive
+    EXPECT(L.cell_n >= 0 && L.cell_n <= RT_CELL_MAX);
+    if (!L.scan && L.cell_n) EXPECT(L.cell_first == L.nprims);
+    for (size_t i = L.nprims; i < nstaged; i++) EXPECT(prims[i].m[3] >= 0 && prims[i].m[3] < L.nprims);
+    if (L.scan) {
+        EXPECT(L.nprescan == 0 && L.cell_n == 0 && L.ngroups >= 1);
+        int total = 0;
+        for (int g = 0; g < L.ngroups; g++) {
+            rt_dgroup grp;
+            std::memcpy(&grp, L.image.data() + L.groups + g * sizeof grp, sizeof grp);
+            EXPECT(grp.first == total && grp.count > 0);
+            total += grp.count;
+        }
+        EXPECT(total == L.nprims);
+    } else {
+        EXPECT(L.ngroups == 0);
+    }
+    if (!std::strcmp(name, "edge_empty")) {   // nothing but sentinels and the Perlin tables
+        EXPECT(L.has_bvh == 0 && L.nprims == 0 && !L.scan && L.cell_n == 0);
+        EXPECT(sentinels == (int)n - 2 - (d->nmaterials > 0) - (d->ntextures > 0));
+    }
+}
 
 void scenes() {
     const char *names[] = {"final", "random_scene", "cornell_box", "cornell_smoke", "random_motion", "simple_light",
@@ -45,6 +120,13 @@ void scenes() {
             setenv("RTNW_BVH_WIDTH", w, 1);
             const rtnw::BvhResult r = rtnw::build_bvh(d->prims, d->nprims, d->instances, d->time0, d->time1);
             EXPECT((int)r.order.size() == d->nprims);
+            lowering(nm, d);
+            if (w[0] == '2' && !w[1])
+                for (const char *knob : {"RTNW_SCAN", "RTNW_PRESCAN", "RTNW_CELL"}) {
+                    setenv(knob, "0", 1);
+                    lowering(nm, d);
+                    unsetenv(knob);
+                }
         }
         unsetenv("RTNW_BVH_WIDTH");
         // no GPU in the sanitizer run: the upload must fail cleanly (RT_ERR_HIP), not crash

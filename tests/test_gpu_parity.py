@@ -308,7 +308,7 @@ def test_full_resolution_sampled_crops(scene, nx, ny):
 
 
 def test_default_work_item_is_one_sample_in_reference_order():
-    """chunk <= 0 selects one sample per work item (capi.cpp): the resolve then adds
+    """chunk <= 0 selects one sample per work item (capi_render.cpp): the resolve then adds
     the samples one at a time, the reference's `col += temp` order (main.cpp:311), so
     the image equals the single-partial-sum render (chunk = spp) bit for bit."""
     nx, ny, ns = 40, 24, 12
@@ -595,7 +595,7 @@ def test_ball_waves_leave_the_image_bitwise_unchanged(monkeypatch):
 
 
 def test_deep_first_claims_with_chunks_batches_and_cameras(monkeypatch):
-    """Deep pixels first (capi.cpp prepare_job: the pixels whose primary rays enter a dense
+    """Deep pixels first (capi_render.cpp prepare_job: the pixels whose primary rays enter a dense
     medium are claimed first; each pre-made sample start carries its (chunk, job pixel)):
     with chunks of 2 samples, a slab budget of 3 chunks per launch (several batches, so
     c1 - c0 < nchunks_total), two cameras on one scene object (the job cache is keyed by

@@ -332,7 +332,7 @@ def test_math_probe_rejects_bad_arguments():
 
 def test_wave_log_record_size_matches_the_reader():
     """tools/wave_log.py reads the profile variant's per-wave records (RTNW_WAVE_LOG) in
-    RT_WAVE_LOG_WORDS words each (rt_kernel.h; capi.cpp sizes the buffer by it)."""
+    RT_WAVE_LOG_WORDS words each (rt_kernel.h; capi_render.cpp sizes the buffer by it)."""
     import re
     hdr = open(os.path.join(ROOT, "peter-shirley-ray-tracing-the-next-week_amd", "csrc", "hip", "rt_kernel.h")).read()
     words = int(re.search(r"#define RT_WAVE_LOG_WORDS (\d+)", hdr).group(1))

@@ -198,7 +198,7 @@ def test_cross_group_ties_of_scan64_own_chains_are_in_view():
     assert {54, 56, 58, 59, 60, 61, 62, 63} <= seen and not {55, 57} & seen, sorted(seen)
 
 
-# ------------------------------------------------------------------ the medium cell, by capi.cpp's rule
+# ------------------------------------------------------------------ the medium cell, by scene_lower.cpp's rule
 def prim_box(d, pr):
     """World box of a primitive over the shutter span [0, 1] (bvh.cpp prim_bounds without its
     outward padding, which is far below the margins the cases leave)."""
@@ -229,7 +229,7 @@ def prim_box(d, pr):
 
 
 def cell_choice(d):
-    """capi.cpp's medium-cell choice restated: (medium index or None, its near primitives) and
+    """scene_lower.cpp's medium-cell choice restated: (medium index or None, its near primitives) and
     the number of deep-first balls.  A candidate is a medium bounded by one un-instanced sphere
     (c, R); near = the primitives whose boxes come within R + R / 64 + 1e-3 |c|max of c; the
     cell goes to the first candidate of strictly greatest density with 1..RT_CELL_MAX = 4 near
@@ -264,7 +264,7 @@ def cell_choice(d):
 def test_medium_cell_choice_of_the_cases(name, medium, nnear, deep):
     """RTNW_CELL=0 in tests/test_gpu_generated.py proves something only where the cell is taken,
     and no rt_stats field shows that: the choice is recomputed here from each descriptor by
-    capi.cpp's rule, so the cases' intent (4 near primitives taken, 5 declined, ...) is asserted."""
+    scene_lower.cpp's rule, so the cases' intent (4 near primitives taken, 5 declined, ...) is asserted."""
     d = G.build(G.BY_NAME[name])[0].contents
     got_medium, near, got_deep = cell_choice(d)
     print(f"{name}: cell medium {got_medium}, near primitives {near}, deep balls {got_deep}")

@@ -7,6 +7,7 @@ and ``-fno-sanitize-recover=all``, so any finding aborts the driver.  Leak detec
 off for the host driver: the reference's scene API allocates its hitables with ``new``
 and never frees them (main.cpp builders), which the host API mirrors on purpose.
 """
+import glob
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -16,7 +17,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "peter-shirley-ray-tracing-the-next-week_amd")
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
-HOST_SOURCES = ["capi.cpp", "bvh.cpp", "flatten.cpp", "rtnw.cpp", "png.cpp", "dist.cpp"]
+HOST_SOURCES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(PKG, "csrc", "host", "*.cpp")))
 
 
 def _env():
