@@ -88,8 +88,7 @@ static int render_adaptive(const char *fn, rt_scene *s, const rt_camera_desc *ca
     const int cap = p->spp;
     int done = ap->min_spp, added = ap->min_spp;
     uint32_t nactive = npix;
-    std::vector<uint8_t> deep;   // the frame's deep pixels (prepare_job's order: they go first)
-    std::vector<uint32_t> rxy, rslot;   // the other active pixels of a pass, appended after the deep ones
+    rtnw::ActiveJobState order;   // the deep map (deep pixels go first, as in a tile job) and the sweep's scratch lists
     const bool deep_front = deep_first(s);
     for (;;) {
         st.passes += 1;
@@ -116,48 +115,9 @@ static int render_adaptive(const char *fn, rt_scene *s, const rt_camera_desc *ca
         t_select += clock_ms() - t0;
         if (!more || nactive == 0) break;
         t0 = clock_ms();
-        if (deep_front && deep.empty()) {
-            deep.resize(npix);
-            for (int yy = 0; yy < h; yy++)
-                for (int xx = 0; xx < w; xx++) deep[(size_t)yy * w + xx] = deep_pixel(s, cam, x0 + xx, y0 + yy, p->nx, p->ny);
-        }
-        // the active pixels, the deep ones first; each group block by block, a block column by
-        // column.  One sweep without a branch on the flags (they are as good as random): every
-        // pixel is written to the end of both lists, and a list grows only if the pixel is its own.
-        uint32_t n = 0, nr = 0;
-        if (deep_front && rxy.empty()) {
-            rxy.resize((size_t)npix + 1);
-            rslot.resize((size_t)npix + 1);
-        }
-        for (int by = 0; by < h; by += 8)
-            for (int bx = 0; bx < w; bx += 8)
-                for (int xx = bx; xx < std::min(bx + 8, w); xx++)
-                    for (int yy = by; yy < std::min(by + 8, h); yy++) {
-                        const uint32_t o = (uint32_t)yy * (uint32_t)w + (uint32_t)xx;
-                        const uint32_t v = (uint32_t)(x0 + xx) | ((uint32_t)(y0 + yy) << 16);
-                        const uint32_t on = flags[o] != 0;
-                        if (deep_front) {
-                            const uint32_t d = deep[o] != 0;
-                            rxy[nr] = v;
-                            rslot[nr] = o;
-                            nr += on & (d ^ 1u);
-                            xy[n] = v;
-                            slot[n] = o;
-                            n += on & d;
-                        } else {
-                            xy[n] = v;
-                            slot[n] = o;
-                            n += on;
-                        }
-                    }
-        const uint32_t ndeep = deep_front ? n : 0;
-        if ((uint64_t)n + nr > npix) return fail(RT_ERR_HIP, f + ": pixel list overflow");
-        if (nr) {
-            std::memcpy(xy + n, rxy.data(), (size_t)nr * sizeof(uint32_t));
-            std::memcpy(slot + n, rslot.data(), (size_t)nr * sizeof(uint32_t));
-            n += nr;
-        }
-        if (n != nactive) return fail(RT_ERR_HIP, f + ": the active flags and their count disagree");
+        if (deep_front && order.deep.empty()) rtnw::fill_deep_map(*s, cam, x0, y0, w, h, p->nx, p->ny, &order.deep);
+        uint32_t ndeep = 0;
+        if (int rc = rtnw::active_job_order(f, flags, x0, y0, w, h, nactive, &order, xy, slot, &ndeep)) return rc;
         added = std::min(ap->step_spp, cap - done);
         q.spp = added;
         q.sample_offset = (uint32_t)done;

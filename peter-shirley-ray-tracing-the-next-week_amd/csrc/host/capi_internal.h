@@ -12,6 +12,7 @@
 #include "../rt_layout.h"
 #include "../hip/rt_kernel.h"
 #include "scene_lower.h"
+#include "job_plan.h"
 
 inline int fail(int code, const std::string &msg) { return rt_internal_fail(code, msg); }
 inline int hip_fail(hipError_t e, const char *what) {
@@ -28,11 +29,16 @@ inline int env_int(const char *name, int dflt, int lo, int hi) {
     return dflt;
 }
 
-// A device buffer kept between calls and grown on demand (the old allocation is freed
-// first; it never shrinks), and its sibling in pinned host memory.
+// A device buffer grown on demand (the old allocation is freed first; it never shrinks), its
+// sibling in pinned host memory, and a set of events.  Each owns what it holds: whoever holds
+// one (a scene, a call's frame) frees it by going away, error paths included.
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t n) {
         if (n <= bytes) return RT_OK;
         release();
@@ -49,6 +55,10 @@ struct DevBuf {
 struct PinBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
     int reserve(size_t n) {
         if (n <= bytes) return RT_OK;
         release();
@@ -62,7 +72,20 @@ struct PinBuf {
         bytes = 0;
     }
 };
+template <int N>
+struct Events {   // created by the holder (hipEventCreate(&ev[k])), destroyed here
+    hipEvent_t e[N] = {};
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipEvent_t &operator[](int k) { return e[k]; }
+};
 
+// Destroyed by `delete` with its device current (rt_scene_destroy): every member frees itself.
 struct rt_scene : rtnw::SceneInfo {
     int device = 0;
     int cus = 0;
@@ -71,23 +94,27 @@ struct rt_scene : rtnw::SceneInfo {
     int stack_depth = 0;          // its traversal stack entries per lane
     hipStream_t own_stream = nullptr;
     // scene in HBM: one allocation (arena) holding the arrays below (rtnw::LoweredScene's image)
-    void *arena = nullptr;
+    DevBuf arena;
     void *nodes = nullptr, *prims = nullptr, *bprims = nullptr, *media = nullptr, *mats = nullptr, *texs = nullptr,
          *insts = nullptr, *ranvec = nullptr, *perm = nullptr, *texels = nullptr, *groups = nullptr;
     // job cache
     std::vector<int32_t> job_tiles;
     uint32_t job_ndeep = 0;                 // the job's first job_ndeep pixels are the deep ones (prepare_job)
     uint32_t npix = 0;
-    void *job_xy = nullptr, *job_out = nullptr;
-    size_t job_cap = 0;           // pixels job_xy and job_out have room for
+    DevBuf job_xy, job_out;       // the job's pixel lists (both have room for the same number of pixels)
     DevBuf slab;
     DevBuf acc;                   // per-pixel running sums between sample batches
     DevBuf frame;                 // rt_render_adaptive: the frame's sums, moments, counts and flags ...
     PinBuf pin;                   // ... and pinned host memory for the passes' pixel lists, flags and counters
     DevBuf fold;                  // RT_FLAG_RIGHT_FOLD: the lanes' attenuation stacks (rt_kernel.h RtKernelArgs.fold)
-    void *counter = nullptr, *stats = nullptr;
+    DevBuf counter;               // the work counter (64 B), then the statistics counters ...
+    void *stats = nullptr;        // ... which start here
     DevBuf host_out;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    Events<3> ev;
+    rt_scene() = default;
+    ~rt_scene() {
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
 };
 
 // internal to the library: not among its dynamic symbols
@@ -101,7 +128,6 @@ int ensure_own_stream(rt_scene *s);   // created on first use (rt_scene_create)
 void fill_scene_args(const rt_scene *s, RtKernelArgs &a);
 void fill_camera_args(const rt_camera_desc *cam, const rt_render_params *p, RtKernelArgs &a);
 bool deep_first(const rt_scene *s);
-bool deep_pixel(const rt_scene *s, const rt_camera_desc *cam, int x, int y, int nx, int ny);
 struct JobSlots {
     const uint32_t *xy, *slot;
     uint32_t n, ndeep;

@@ -43,10 +43,8 @@ static int features_run(rt_scene *s, const rt_camera_desc *cam, const rt_render_
                         float *guides_dev, hipStream_t stream) {
     const uint32_t npix = (uint32_t)w * (uint32_t)h;   // <= 65535^2
     const uint64_t sample_bytes = (uint64_t)npix * RT_GUIDE_FLOATS * sizeof(float);
-    uint64_t per = std::max<uint64_t>(1, RT_FEATURE_SLAB_BYTES / sample_bytes);
-    per = std::min<uint64_t>(per, std::max<uint64_t>(1, 0x7FFFFFFFull / npix));
-    per = std::min<uint64_t>(per, (uint64_t)p->spp);
-    if ((uint64_t)npix * per >= 0x80000000ull) return fail(RT_ERR_INVALID, "rt_render_features: rectangle too large");
+    uint64_t per = 0;
+    if (int rc = rtnw::plan_feature_batches(npix, p->spp, RT_GUIDE_FLOATS * sizeof(float), RT_FEATURE_SLAB_BYTES, &per)) return rc;
     if (int rc = s->slab.reserve((size_t)(sample_bytes * per))) return rc;
     // the pass reads the scene's arrays and the camera (rt_features.hip), none of the
     // megakernel's launch knobs
@@ -84,11 +82,18 @@ static int denoise_check(const char *fn, int nx, int ny, bool nulls, const rt_de
     return RT_OK;
 }
 
-// The filter's planes (G, E ping, E pong: 48 B per pixel) per device, grown on demand.
+// The filter's planes (G, E ping, E pong: 48 B per pixel), one buffer per device, grown on
+// demand.  A call holds g_dn_mu from the lookup until its last launch is enqueued: a concurrent
+// call that must grow the buffer then frees it only after that, and hipFree waits for the
+// device, so no enqueued launch reads freed memory.  The map lives as long as the process and
+// is leaked on purpose: destroying it would call hipFree during static destruction, after the
+// HIP runtime may have shut down.
 namespace {
-struct DenoiseWorkspace { void *p = nullptr; size_t bytes = 0; };
 std::mutex g_dn_mu;
-std::map<int, DenoiseWorkspace> g_dn_ws;
+std::map<int, DevBuf> &denoise_workspaces() {
+    static auto *ws = new std::map<int, DevBuf>;
+    return *ws;
+}
 }
 
 static int denoise_run(int device, int nx, int ny, const float *color, const float *guides, const float *moments,
@@ -98,19 +103,10 @@ static int denoise_run(int device, int nx, int ny, const float *color, const flo
         HIP_TRY(hipMemcpyAsync(out, color, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream));
         return RT_OK;
     }
-    float4 *planes = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_dn_mu);
-        DenoiseWorkspace &ws = g_dn_ws[device];
-        if (npix * 48 > ws.bytes) {
-            if (ws.p) (void)hipFree(ws.p);
-            ws.p = nullptr;
-            ws.bytes = 0;
-            HIP_TRY(hipMalloc(&ws.p, npix * 48));
-            ws.bytes = npix * 48;
-        }
-        planes = (float4 *)ws.p;
-    }
+    std::lock_guard<std::mutex> lock(g_dn_mu);
+    DevBuf &ws = denoise_workspaces()[device];
+    if (int rc = ws.reserve(npix * 48)) return rc;
+    float4 *planes = (float4 *)ws.p;
     float4 *G = planes, *E[2] = {planes + npix, planes + 2 * npix};
     HIP_TRY(rt_denoise_launch.prepare((uint32_t)npix, color, guides, moments, spp, dp->uniform_spp, dp->demodulate != 0, G,
                                       E[0], stream));
@@ -179,17 +175,10 @@ int rt_denoise(int device, int nx, int ny, const float *color, const float *albe
     // one allocation: colour, guides, moments, spp, out
     const size_t off_g = npix * 3, off_m = off_g + npix * RT_GUIDE_FLOATS, off_s = off_m + npix * 2, off_o = off_s + npix,
                  total = off_o + npix * 3;
-    float *d = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Guard {
-        float *&d;
-        hipEvent_t *ev;
-        ~Guard() {
-            if (d) (void)hipFree(d);
-            for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
-        }
-    } guard{d, ev};
-    HIP_TRY(hipMalloc((void **)&d, total * sizeof(float)));
+    DevBuf staging;
+    Events<2> ev;
+    if (int rc = staging.reserve(total * sizeof(float))) return rc;
+    float *d = (float *)staging.p;
     HIP_TRY(hipMemcpy(d, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d + off_g, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
     if (moments) HIP_TRY(hipMemcpy(d + off_m, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));

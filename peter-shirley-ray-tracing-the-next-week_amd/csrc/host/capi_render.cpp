@@ -8,15 +8,6 @@
 
 namespace {
 
-template <class T>
-int upload(void **dst, const std::vector<T> &v) {
-    *dst = nullptr;
-    if (v.empty()) return RT_OK;
-    HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
-    HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return RT_OK;
-}
-
 // SURVEY §8d byte model (bytes the algorithm must read or write, independent of
 // this implementation's record padding):
 //   node fetch: the bytes loaded per visit (BVH2 64 B, BVH4 112 B, BVH8 224 B, compressed
@@ -53,9 +44,6 @@ int ball_waves() {
     return RT_BALL_WAVES;
 }
 
-// Small claims per wave at the end of a launch (render_tiles' claim sizes).
-#define RT_TAIL_CLAIMS 32
-
 // Partial-sum slab budget per launch (bytes; env RTNW_SLAB_BUDGET overrides, for tests).
 // A job whose slab would be larger runs as several launches over sample batches.
 // 16 GiB of the 288 GiB HBM: config 5 on one GPU (1e9 samples, 12 GB) is one launch,
@@ -69,16 +57,19 @@ uint64_t slab_budget() {
     return RT_SLAB_BUDGET;
 }
 
-void free_job_lists(rt_scene *s) {
-    if (s->job_xy) { (void)hipFree(s->job_xy); s->job_xy = nullptr; }
-    if (s->job_out) { (void)hipFree(s->job_out); s->job_out = nullptr; }
-    s->job_cap = 0;
+// Room for n pixels in both job lists, or neither list.
+int reserve_job_lists(rt_scene *s, size_t n) {
+    int rc = s->job_xy.reserve(n * sizeof(uint32_t));
+    if (rc == RT_OK) rc = s->job_out.reserve(n * sizeof(uint32_t));
+    if (rc != RT_OK) {
+        s->job_xy.release();
+        s->job_out.release();
+    }
+    return rc;
 }
 
-// Job pixel order: tiles in the order given; inside a tile, bands of 8 rows listed
-// column by column (8 pixels per column), so that ANY 64 consecutive items — a wave
-// claim, wherever it starts — are 8 neighbouring columns of one band (coherent
-// primary rays), also when the tile width is not a multiple of 8 (500 = 62.5 x 8).
+// The tile job's pixel lists (rtnw::tile_job_order), kept on the device until a job with
+// another key comes.
 int prepare_job(rt_scene *s, const int32_t *tiles, int ntiles, int nx, int ny, const rt_camera_desc *cam) {
     std::vector<int32_t> key(tiles, tiles + 4 * ntiles);
     // the deep-first order depends on the camera: its rays' frame joins the cache key
@@ -91,43 +82,20 @@ int prepare_job(rt_scene *s, const int32_t *tiles, int ntiles, int nx, int ny, c
         for (const float *f : cf)
             for (int k = 0; k < 3; k++) { int32_t b; std::memcpy(&b, &f[k], 4); key.push_back(b); }
     }
-    if (key == s->job_tiles && s->job_xy) return RT_OK;
+    if (key == s->job_tiles && s->job_xy.p) return RT_OK;
     std::vector<uint32_t> xy, oi;
-    uint32_t base = 0;
-    for (int t = 0; t < ntiles; t++) {
-        const int x0 = tiles[4 * t], y0 = tiles[4 * t + 1], w = tiles[4 * t + 2], h = tiles[4 * t + 3];
-        if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 + w > nx || y0 + h > ny || nx > 65535 || ny > 65535)
-            return fail(RT_ERR_INVALID, "tile outside the image");
-        for (int by = 0; by < h; by += 8)
-            for (int xx = 0; xx < w; xx++)
-                for (int yy = by; yy < std::min(by + 8, h); yy++) {
-                    xy.push_back((uint32_t)(x0 + xx) | ((uint32_t)(y0 + yy) << 16));
-                    oi.push_back(base + (uint32_t)(yy * w + xx));
-                }
-        base += (uint32_t)(w * h);
-    }
-    // deep pixels first, each group in the band order above (a claim of 64 consecutive
-    // items stays 64 neighbouring pixels of one group)
     uint32_t ndeep = 0;
-    if (deep) {
-        std::vector<uint32_t> dxy, doi, rxy, roi;
-        for (size_t i = 0; i < xy.size(); i++) {
-            const bool in = deep_pixel(s, cam, (int)(xy[i] & 0xFFFFu), (int)(xy[i] >> 16), nx, ny);
-            (in ? dxy : rxy).push_back(xy[i]);
-            (in ? doi : roi).push_back(oi[i]);
-        }
-        ndeep = (uint32_t)dxy.size();
-        if (ndeep == xy.size()) ndeep = 0;   // all deep: one group
-        dxy.insert(dxy.end(), rxy.begin(), rxy.end());
-        doi.insert(doi.end(), roi.begin(), roi.end());
-        xy.swap(dxy);
-        oi.swap(doi);
-    }
-    free_job_lists(s);
+    rtnw::DeepTest test;
+    if (deep) test = [=](int x, int y) { return rtnw::deep_pixel(*s, cam, x, y, nx, ny); };
+    if (int rc = rtnw::tile_job_order(tiles, ntiles, nx, ny, test, &xy, &oi, &ndeep)) return rc;
+    // the old lists are freed, not reused: hipFree waits for the device, so a launch of the
+    // previous job that still reads them (on a stream of the caller's) ends before the copies below
+    s->job_xy.release();
+    s->job_out.release();
     s->job_tiles.clear();
-    if (int rc = upload(&s->job_xy, xy)) return rc;
-    if (int rc = upload(&s->job_out, oi)) return rc;
-    s->job_cap = xy.size();
+    if (int rc = reserve_job_lists(s, xy.size())) return rc;
+    HIP_TRY(hipMemcpy(s->job_xy.p, xy.data(), xy.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->job_out.p, oi.data(), oi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     s->npix = (uint32_t)xy.size();
     s->job_ndeep = ndeep;
     s->job_tiles = key;
@@ -148,14 +116,9 @@ int prepare_job_slots(rt_scene *s, const JobSlots &js, int nx, int ny, hipStream
     for (uint32_t i = 0; i < js.n; i++)
         if ((int)(js.xy[i] & 0xFFFFu) >= nx || (int)(js.xy[i] >> 16) >= ny) return fail(RT_ERR_INVALID, "job pixel outside the image");
     s->job_tiles.clear();
-    if (!s->job_xy || !s->job_out || js.n > s->job_cap) {
-        free_job_lists(s);
-        HIP_TRY(hipMalloc(&s->job_xy, (size_t)js.n * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&s->job_out, (size_t)js.n * sizeof(uint32_t)));
-        s->job_cap = js.n;
-    }
-    HIP_TRY(hipMemcpyAsync(s->job_xy, js.xy, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(s->job_out, js.slot, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (int rc = reserve_job_lists(s, js.n)) return rc;
+    HIP_TRY(hipMemcpyAsync(s->job_xy.p, js.xy, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(s->job_out.p, js.slot, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     s->npix = js.n;
     s->job_ndeep = js.ndeep == js.n ? 0 : js.ndeep;   // all deep: one group
     return RT_OK;
@@ -300,25 +263,6 @@ bool deep_first(const rt_scene *s) {
     return v;
 }
 
-bool deep_pixel(const rt_scene *s, const rt_camera_desc *cam, int x, int y, int nx, int ny) {
-    // the pixel centre's primary ray (main.cpp:305-306, camera.h:52-55 without jitter or lens)
-    const float u = (x + 0.5f) / nx, v = (ny - 1 - y + 0.5f) / ny;
-    float o[3], d[3];
-    for (int k = 0; k < 3; k++) {
-        o[k] = cam->origin[k];
-        d[k] = cam->lower_left_corner[k] + u * cam->horizontal[k] + v * cam->vertical[k] - o[k];
-    }
-    for (size_t b = 0; b + 3 < s->deep_balls.size(); b += 4) {
-        const float *c = &s->deep_balls[b];
-        const double oc[3] = {o[0] - (double)c[0], o[1] - (double)c[1], o[2] - (double)c[2]};
-        const double a = (double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2];
-        const double bb = oc[0] * d[0] + oc[1] * d[1] + oc[2] * d[2];
-        const double cc = oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2] - (double)c[3] * c[3];
-        if (bb * bb - a * cc > 0 && (bb < 0 || cc < 0)) return true;
-    }
-    return false;
-}
-
 // The body of rt_render_tiles and rt_render_tiles_moments: the job is the tile list, or `js`
 // when non-null; with mom_dev the resolve is rt_moments.hip's, which also keeps the moments.
 int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
@@ -349,26 +293,13 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     if (int rc = js ? prepare_job_slots(s, *js, p->nx, p->ny, stream) : prepare_job(s, tiles, ntiles, p->nx, p->ny, cam))
         return rc;
 
-    // Work item = `chunk` samples of one pixel, one by default: short items keep each
-    // wave's lanes on neighbouring pixels (a wave deals its claims to lanes as they free
-    // up; long items let its pixels drift apart): 16 -> 1 sample per item is 92.2 ->
-    // 81.8 ms on c4.  The partial-sum slab holds one rgb (12 B) per item
-    // of a launch; a job whose slab would pass the budget runs as several launches
-    // over sample batches (whole chunks), and the resolve adds every batch to a
-    // per-pixel running sum in sample order — so the sum is the same sequence of
-    // float adds whatever the batch size, i.e. the image does not depend on the job's
-    // size (one GPU or a rank's share of eight).
+    // the job's sample batches (rtnw::plan_batches: one partial sum, rgb, per work item)
     const int chunk = p->chunk > 0 ? p->chunk : 1;
-    const uint64_t nchunks_total = ((uint64_t)p->spp + chunk - 1) / chunk;
-    const uint64_t max_items = 0xFFFFFFFFull - 64;
-    if ((uint64_t)s->npix > max_items) return fail(RT_ERR_INVALID, "job too large (pixels >= 2^32)");
-    const uint64_t item_bytes = 4 * (uint64_t)rt_slab_floats();   // one partial sum (rgb)
-    uint64_t per = std::max<uint64_t>(1, slab_budget() / ((uint64_t)s->npix * item_bytes));
-    per = std::min<uint64_t>(per, max_items / s->npix);
-    per = std::min<uint64_t>(per, nchunks_total);
-    const uint64_t nbatches = (nchunks_total + per - 1) / per;
-    per = (nchunks_total + nbatches - 1) / nbatches;   // batches of (nearly) equal size, as many
-    if (int rc = s->slab.reserve((size_t)s->npix * per * item_bytes)) return rc;
+    const uint64_t item_bytes = 4 * (uint64_t)rt_slab_floats();
+    rtnw::BatchPlan plan;
+    if (int rc = rtnw::plan_batches(s->npix, p->spp, chunk, slab_budget(), item_bytes, &plan)) return rc;
+    const uint64_t nbatches = plan.nbatches, nchunks_total = plan.nchunks_total;
+    if (int rc = s->slab.reserve((size_t)s->npix * plan.per * item_bytes)) return rc;
     if (int rc = s->acc.reserve(nbatches > 1 ? (size_t)s->npix * 16 : 0)) return rc;
     if (int rc = s->fold.reserve(fold_bytes)) return rc;
     const bool count = (p->flags & RT_FLAG_COUNT) != 0;
@@ -392,26 +323,22 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     a.max_depth = p->max_depth;
     a.background = p->background;
     a.chunk = chunk;
-    a.job_xy = (const uint32_t *)s->job_xy;
+    a.job_xy = (const uint32_t *)s->job_xy.p;
     a.npix = s->npix;
     a.slab = (float *)s->slab.p;
-    a.counter = (uint32_t *)s->counter;
+    a.counter = (uint32_t *)s->counter.p;
     a.stats = (unsigned long long *)s->stats;
     // RTNW_WAVE_LOG=<file> with RT_FLAG_PROFILE: every wave's timeline appended to the
     // file as 5 uint64 (start, pool dry, end in s_memrealtime ticks, xcc << 32 | HW_ID,
     // items claimed) per wave and batch (tools/tail_probe.py --wave-log; diagnostics)
     const char *wave_log_path = prof ? std::getenv("RTNW_WAVE_LOG") : nullptr;
-    unsigned long long *wave_log = nullptr;
-    struct FreeOnExit {   // every return below, error paths included, frees the log buffer
-        unsigned long long *&p;
-        ~FreeOnExit() { if (p) (void)hipFree(p); }
-    } wave_log_guard{wave_log};
+    DevBuf wave_log;   // freed by every return below, error paths included
     const size_t wave_log_n = (size_t)s->grid[2] * ((s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK) / 64) * RT_WAVE_LOG_WORDS;
     if (wave_log_path) {
-        HIP_TRY(hipMalloc(&wave_log, wave_log_n * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(wave_log, 0, wave_log_n * sizeof(unsigned long long), stream));
+        if (int rc = wave_log.reserve(wave_log_n * sizeof(unsigned long long))) return rc;
+        HIP_TRY(hipMemsetAsync(wave_log.p, 0, wave_log_n * sizeof(unsigned long long), stream));
     }
-    a.wave_log = wave_log;
+    a.wave_log = (unsigned long long *)wave_log.p;
     a.fold = fold ? (float4 *)s->fold.p : nullptr;
     a.fold_stride = (uint32_t)fold_lanes;
 
@@ -420,36 +347,24 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     const float k = (float)(1.0 / (double)(float)ns_total);
     const uint64_t waves = (uint64_t)s->grid[mode] * ((s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK) / 64);
     double kernel_ms = 0, resolve_ms = 0;
+    // RTNW_CLAIM (x 64 items) and RTNW_TAIL_CLAIMS override the claim sizes (tests, A/B runs); -1: none
+    const char *ec = std::getenv("RTNW_CLAIM"), *et = std::getenv("RTNW_TAIL_CLAIMS");
+    const int claim_x64 = ec ? std::max(1, std::atoi(ec)) : -1, tail_claims = et ? std::max(0, std::atoi(et)) : -1;
     for (uint64_t b = 0; b < nbatches; ++b) {
-        const uint64_t c0 = b * per, c1 = std::min(c0 + per, nchunks_total);
-        const uint64_t s0 = c0 * (uint64_t)chunk, s1 = std::min<uint64_t>(c1 * (uint64_t)chunk, (uint64_t)p->spp);
-        a.ns = (int)(s1 - s0);                                   // samples of this batch
-        a.sample_offset = p->sample_offset + (uint32_t)s0;       // their first sample index
-        a.nchunks = (int)(c1 - c0);
-        const uint64_t nitems = (uint64_t)s->npix * (c1 - c0);
-        a.nitems = (uint32_t)nitems;
+        const rtnw::BatchLaunch l = rtnw::plan_batch(plan, b, s->npix, p->spp, chunk, p->sample_offset, waves, s->job_ndeep,
+                                                     claim_x64, tail_claims);
+        a.ns = l.ns;
+        a.sample_offset = l.sample_offset;
+        a.nchunks = l.nchunks;
+        a.nitems = l.nitems;
         a.ndeep = s->job_ndeep;
-        a.ndeep_items = (uint32_t)((uint64_t)s->job_ndeep * (c1 - c0));
-        // Claim size: up to 512 items per atomic (64 -> 512 is 81.6 -> 76.9 ms on c4:
-        // fewer round trips to the one contended counter), at least 8
-        // claims per wave so that small jobs still spread over every wave.
-        // The last RT_TAIL_CLAIMS claims per wave are of 64 items: with 512-item claims
-        // to the end, the waves ran dry over 2.4 ms (the first found the pool empty at
-        // 54.1 ms of a 57.1-ms launch, the last at 56.5; with 64-item claims over 0.5 ms,
-        // but every claim is a round trip to the one device-scope counter:
-        // tools/tail_probe.py).
-        {
-            uint64_t c = std::min<uint64_t>(std::max<uint64_t>(nitems / (waves * 8) / 64 * 64, 64), 512);
-            uint64_t tail = 64 * RT_TAIL_CLAIMS * waves;
-            if (const char *e = std::getenv("RTNW_CLAIM")) c = (uint64_t)std::max(1, std::atoi(e)) * 64;   // x 64 items
-            if (const char *e = std::getenv("RTNW_TAIL_CLAIMS")) tail = 64 * (uint64_t)std::max(0, std::atoi(e)) * waves;
-            a.claim = (uint32_t)c;
-            a.claim_tail = 64;
-            a.nbig = (uint32_t)(nitems > tail ? (nitems - tail) / c : 0);
-        }
+        a.ndeep_items = l.ndeep_items;
+        a.claim = l.claim;
+        a.claim_tail = l.claim_tail;
+        a.nbig = l.nbig;
         const int rmode = (b == 0 ? RT_RESOLVE_FIRST : 0) | (b + 1 == nbatches ? RT_RESOLVE_LAST : 0) |
                           (sum_in ? RT_RESOLVE_SUM_IN : 0) | (sum_out ? RT_RESOLVE_RAW : 0);
-        HIP_TRY(hipMemsetAsync(s->counter, 0, 64, stream));
+        HIP_TRY(hipMemsetAsync(s->counter.p, 0, 64, stream));
         // the wave timeline describes the last batch: its slots start from zero each launch
         if (prof)
             HIP_TRY(hipMemsetAsync((unsigned long long *)s->stats + RT_STAT_TIME, 0, 7 * sizeof(unsigned long long), stream));
@@ -458,15 +373,15 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
         HIP_TRY(hipEventRecord(s->ev[1], stream));
         if (mom_dev)
             HIP_TRY(rt_moments_launch.resolve((const float *)s->slab.p, rt_slab_floats(), s->npix, a.nchunks, k,
-                                             (float4 *)s->acc.p, rmode, (const uint32_t *)s->job_out, out_dev, mom_dev,
+                                             (float4 *)s->acc.p, rmode, (const uint32_t *)s->job_out.p, out_dev, mom_dev,
                                              stream));
         else
             HIP_TRY(rt_launch_resolve((const float *)s->slab.p, s->npix, a.nchunks, k, (float4 *)s->acc.p, rmode,
-                                      (const uint32_t *)s->job_out, out_dev, stream));
+                                      (const uint32_t *)s->job_out.p, out_dev, stream));
         HIP_TRY(hipEventRecord(s->ev[2], stream));
-        if (wave_log) {
+        if (wave_log.p) {
             std::vector<unsigned long long> h(wave_log_n);   // the render stream may be non-blocking
-            HIP_TRY(hipMemcpyAsync(h.data(), wave_log, h.size() * sizeof h[0], hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(h.data(), wave_log.p, h.size() * sizeof h[0], hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             if (FILE *f = std::fopen(wave_log_path, "ab")) {
                 std::fwrite(h.data(), sizeof h[0], h.size(), f);

@@ -1,5 +1,6 @@
 // capi_scene.cpp — rt_scene_create / rt_scene_destroy: the lowered scene (scene_lower.cpp)
 // uploaded to HBM, and what its launches need from the device (grid, LDS variant).
+#include <memory>
 #include <mutex>
 
 #include "capi_internal.h"
@@ -83,12 +84,6 @@ extern "C" {
 void rt_scene_destroy(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    for (void *p : {s->arena, s->job_xy, s->job_out, s->counter})
-        if (p) (void)hipFree(p);
-    for (DevBuf *b : {&s->slab, &s->acc, &s->frame, &s->fold, &s->host_out}) b->release();
-    s->pin.release();
-    for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
-    if (s->own_stream) (void)hipStreamDestroy(s->own_stream);
     delete s;
 }
 
@@ -108,14 +103,13 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out) {
     if (int rc = rtnw::lower_scene(d, &low)) return rc;   // (traces "BVH build" and "device records")
     trace.last = rtnw::clock_ms();
 
-    auto *s = new rt_scene();
+    std::unique_ptr<rt_scene> s(new rt_scene());   // an error return below frees what it holds by then
     static_cast<rtnw::SceneInfo &>(*s) = low;
     s->device = device;
-    auto cleanup = [&](int rc) { rt_scene_destroy(s); return rc; };
-    if ((e = hipMalloc(&s->arena, low.image.size())) != hipSuccess) return cleanup(hip_fail(e, "hipMalloc scene arena"));
-    if ((e = hipMemcpy(s->arena, low.image.data(), low.image.size(), hipMemcpyHostToDevice)) != hipSuccess)
-        return cleanup(hip_fail(e, "hipMemcpy scene arena"));
-    uint8_t *base = (uint8_t *)s->arena;
+    if (int rc = s->arena.reserve(low.image.size())) return rc;
+    if ((e = hipMemcpy(s->arena.p, low.image.data(), low.image.size(), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy scene arena");
+    uint8_t *base = (uint8_t *)s->arena.p;
     s->nodes = base + low.nodes;
     s->prims = base + low.prims;
     s->bprims = base + low.bprims;
@@ -129,17 +123,16 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out) {
     s->texels = base + low.texels;
     trace("upload (one allocation)");
 
-    if (int rc = device_attributes(s)) return cleanup(rc);
+    if (int rc = device_attributes(s.get())) return rc;
     trace("device attributes");
     // the work counter (64 B) and the statistics counters in one allocation
-    if ((e = hipMalloc(&s->counter, 64 + RT_STATS_LEN * sizeof(unsigned long long))) != hipSuccess)
-        return cleanup(hip_fail(e, "hipMalloc counters"));
-    s->stats = (uint8_t *)s->counter + 64;
+    if (int rc = s->counter.reserve(64 + RT_STATS_LEN * sizeof(unsigned long long))) return rc;
+    s->stats = (uint8_t *)s->counter.p + 64;
     trace("counters");
-    for (auto &ev : s->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return cleanup(hip_fail(e, "hipEventCreate"));
+    for (int k = 0; k < 3; k++)
+        if ((e = hipEventCreate(&s->ev[k])) != hipSuccess) return hip_fail(e, "hipEventCreate");
     trace("events");
-    *out = s;
+    *out = s.release();
     return RT_OK;
 }
 

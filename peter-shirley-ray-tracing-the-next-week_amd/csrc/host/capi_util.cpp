@@ -55,13 +55,13 @@ int rt_math_probe(int fn, const float *a, const float *b, float *out, int64_t n)
         return fail(RT_ERR_INVALID, "rt_math_probe: bad arguments");
     if (n == 0) return RT_OK;
     const size_t bytes = (size_t)n * sizeof(float);
-    float *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 3 * bytes));
+    DevBuf buf;
+    if (int rc = buf.reserve(3 * bytes)) return rc;
+    float *d = (float *)buf.p;
     hipError_t e = hipMemcpy(d, a, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && fn >= 4) e = hipMemcpy(d + n, b, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = rt_launch_math_probe(fn, d, d + n, d + 2 * n, (int)n, nullptr);
     if (e == hipSuccess) e = hipMemcpy(out, d + 2 * n, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(e, "rt_math_probe");
     return RT_OK;
 }

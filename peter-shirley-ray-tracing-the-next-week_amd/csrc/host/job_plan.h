@@ -1,0 +1,60 @@
+// job_plan.h — the arithmetic of a render job (job_plan.cpp): the order of its pixels, its
+// sample batches and each launch's claim sizes.  Host arithmetic only, no HIP, so that it
+// runs, and is tested, without a GPU (tests/native/host_sanitize.cpp).
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "scene_lower.h"
+
+#pragma GCC visibility push(hidden)
+namespace rtnw {
+
+// Whether the primary ray through the centre of pixel (x, y) enters one of the scene's dense
+// media first (SceneInfo::deep_balls).
+bool deep_pixel(const SceneInfo &s, const rt_camera_desc *cam, int x, int y, int nx, int ny);
+
+// The pixel lists of a tile job: pixel k of the job is image pixel xy[k] (x | y << 16) and
+// goes to oi[k] of the packed output.  `deep` (x, y) -> bool lists the deep pixels first,
+// ndeep of them (0 when all are deep: one group); empty: no such split.
+using DeepTest = std::function<bool(int, int)>;
+int tile_job_order(const int32_t *tiles, int ntiles, int nx, int ny, const DeepTest &deep, std::vector<uint32_t> *xy,
+                   std::vector<uint32_t> *oi, uint32_t *ndeep);
+
+// The pixel lists of an adaptive pass over the frame (x0, y0, w, h): the pixels whose flag is
+// set, into xy and slot (room for w * h + 1 entries each; slot = yy * w + xx).  With a deep map
+// in the frame's state the deep ones come first, *ndeep of them.  The state also keeps the other
+// group's scratch lists between the frame's passes.
+struct ActiveJobState {
+    std::vector<uint8_t> deep;          // one byte per slot (fill_deep_map); empty: no split
+    std::vector<uint32_t> rxy, rslot;
+};
+void fill_deep_map(const SceneInfo &s, const rt_camera_desc *cam, int x0, int y0, int w, int h, int nx, int ny,
+                   std::vector<uint8_t> *deep);
+int active_job_order(const std::string &who, const uint8_t *flags, int x0, int y0, int w, int h, uint32_t nactive,
+                     ActiveJobState *st, uint32_t *xy, uint32_t *slot, uint32_t *ndeep);
+
+// Sample batches of a render job: `per` chunks of every pixel per launch, nbatches launches.
+struct BatchPlan {
+    uint64_t per, nbatches, nchunks_total;
+};
+int plan_batches(uint64_t npix, int spp, int chunk, uint64_t budget_bytes, uint64_t item_bytes, BatchPlan *out);
+
+// Launch b of a plan: its samples, its items and how the waves claim them (RtKernelArgs).
+// claim_x64 and tail_claims are the overrides RTNW_CLAIM and RTNW_TAIL_CLAIMS, negative: none.
+struct BatchLaunch {
+    int ns;
+    uint32_t sample_offset;
+    int nchunks;
+    uint32_t nitems, ndeep_items, claim, claim_tail, nbig;
+};
+BatchLaunch plan_batch(const BatchPlan &pl, uint64_t b, uint64_t npix, int spp, int chunk, uint32_t sample_offset,
+                       uint64_t waves, uint32_t job_ndeep, int claim_x64, int tail_claims);
+
+// The feature pass's own rule: batches of *per whole samples of every pixel within slab_bytes.
+int plan_feature_batches(uint64_t npix, int spp, uint64_t pixel_bytes, uint64_t slab_bytes, uint64_t *per);
+
+}  // namespace rtnw
+#pragma GCC visibility pop

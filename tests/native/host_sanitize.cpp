@@ -1,7 +1,8 @@
 // tests/native/host_sanitize.cpp — drives the host side of librt_hip.so (scene
 // builders, flattening, every BVH form, the PNG decoder, the C ABI's host-only
 // helpers and its error paths, and the lowering of every built-in scene to the image of the
-// device's arrays, whose invariants are checked here) in a build whose host objects carry
+// device's arrays, whose invariants are checked here, and the job arithmetic of job_plan.cpp:
+// pixel orders, sample batches and claim sizes, as properties) in a build whose host objects carry
 // AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_sanitizers.py; the
 // device code object is linked in unsanitised, as the GPU sanitizer is not
 // available).  Exit 0 = every call returned as expected and no sanitizer fired.
@@ -9,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <fstream>
 #include <iterator>
 #include <string>
@@ -21,6 +23,7 @@
 #include "bvh.h"
 #include "rtnw.h"
 #include "scene_lower.h"
+#include "job_plan.h"
 
 namespace {
 
@@ -224,6 +227,259 @@ void abi_helpers() {
     EXPECT(rt_version() != nullptr);
 }
 
+
+// ---------------------------------------------------------------- job_plan.cpp
+struct Tile { int x0, y0, w, h; };
+
+// The undivided order's rule, per entry: the pixel of output index `o` (tile t, column xx, row
+// yy) and its sort key (tile, band of 8 rows, column, row).
+struct Where { size_t t; int xx, yy; };
+Where where_of(const std::vector<Tile> &tiles, uint32_t o) {
+    uint32_t base = 0;
+    for (size_t t = 0; t < tiles.size(); t++) {
+        const uint32_t n = (uint32_t)tiles[t].w * (uint32_t)tiles[t].h;
+        if (o - base < n) return {t, (int)((o - base) % (uint32_t)tiles[t].w), (int)((o - base) / (uint32_t)tiles[t].w)};
+        base += n;
+    }
+    return {tiles.size(), 0, 0};
+}
+
+void tile_order(const std::vector<Tile> &tiles, int nx, int ny, const rtnw::DeepTest &deep) {
+    std::vector<int32_t> flat;
+    size_t total = 0;
+    for (const Tile &t : tiles) {
+        for (int v : {t.x0, t.y0, t.w, t.h}) flat.push_back(v);
+        total += (size_t)t.w * t.h;
+    }
+    std::vector<uint32_t> xy, oi, dxy, doi;
+    uint32_t nd0 = 7, nd = 7;
+    EXPECT(rtnw::tile_job_order(flat.data(), (int)tiles.size(), nx, ny, rtnw::DeepTest(), &xy, &oi, &nd0) == RT_OK);
+    EXPECT(xy.size() == total && oi.size() == total && nd0 == 0);
+    if (xy.size() != total || oi.size() != total) return;
+    // a permutation of the tiles' pixels, each entry naming its own pixel's place in the output
+    std::vector<uint32_t> pos(total, UINT32_MAX);
+    for (size_t k = 0; k < total; k++) {
+        EXPECT(oi[k] < total && pos[oi[k]] == UINT32_MAX);
+        if (oi[k] >= total) return;
+        pos[oi[k]] = (uint32_t)k;
+        const Where p = where_of(tiles, oi[k]);
+        EXPECT(p.t < tiles.size() && xy[k] == ((uint32_t)(tiles[p.t].x0 + p.xx) | ((uint32_t)(tiles[p.t].y0 + p.yy) << 16)));
+    }
+    // tile after tile; in a tile band after band; a band of r rows is runs of r entries, each one
+    // column with y ascending (r = 8 in a full band: runs start at multiples of 8)
+    size_t k = 0;
+    for (const Tile &t : tiles)
+        for (int by = 0; by < t.h; by += 8) {
+            const int r = std::min(8, t.h - by);
+            for (int xx = 0; xx < t.w; xx++)
+                for (int i = 0; i < r; i++, k++)
+                    EXPECT((int)(xy[k] & 0xFFFFu) == t.x0 + xx && (int)(xy[k] >> 16) == t.y0 + by + i);
+        }
+    if (!deep) return;
+    // deep pixels first, each group in the undivided list's order
+    EXPECT(rtnw::tile_job_order(flat.data(), (int)tiles.size(), nx, ny, deep, &dxy, &doi, &nd) == RT_OK);
+    EXPECT(dxy.size() == total && doi.size() == total);
+    if (dxy.size() != total || doi.size() != total) return;
+    size_t ndeep = 0;
+    for (size_t i = 0; i < total; i++) ndeep += deep((int)(xy[i] & 0xFFFFu), (int)(xy[i] >> 16));
+    EXPECT(nd == (ndeep == total ? 0 : ndeep));
+    for (size_t i = 0; i < total; i++) {
+        EXPECT(doi[i] < total);
+        if (doi[i] >= total) return;
+        EXPECT(dxy[i] == xy[pos[doi[i]]]);
+        EXPECT(deep((int)(dxy[i] & 0xFFFFu), (int)(dxy[i] >> 16)) == (i < ndeep));
+        if (i && i != ndeep) EXPECT(pos[doi[i - 1]] < pos[doi[i]]);
+    }
+}
+
+void tile_orders() {
+    const rtnw::DeepTest half = [](int x, int y) { return 2 * x + 3 * y < 40; };
+    const rtnw::DeepTest all = [](int, int) { return true; };
+    const int sizes[][2] = {{1, 1}, {8, 8}, {9, 7}, {500, 3}};
+    for (const auto &sz : sizes)
+        for (const rtnw::DeepTest &d : {rtnw::DeepTest(), half, all}) tile_order({{0, 0, sz[0], sz[1]}}, sz[0], sz[1], d);
+    for (const rtnw::DeepTest &d : {rtnw::DeepTest(), half}) {
+        tile_order({{3, 2, 5, 11}, {20, 9, 13, 10}}, 40, 24, d);
+        tile_order({{65532, 65532, 3, 3}}, 65535, 65535, d);
+    }
+    tile_order({{65532, 65532, 3, 3}}, 65535, 65535, [](int x, int) { return x == 65534; });
+    // final's own deep balls under the preset camera at 40 x 24, as prepare_job asks
+    rt_scene_desc *d = nullptr;
+    EXPECT(rt_builtin_scene_desc("final", &d) == RT_OK);
+    rtnw::LoweredScene L;
+    if (d) EXPECT(rtnw::lower_scene(d, &L) == RT_OK);
+    EXPECT(!L.deep_balls.empty());
+    rt_camera_desc cam;
+    const float from[3] = {228, 278, -800}, at[3] = {278, 278, 0}, up[3] = {0, 1, 0};
+    EXPECT(rt_camera_init(&cam, from, at, up, 40, 40.0f / 24.0f, 0.0f, 10.0f, 0.0f, 1.0f) == RT_OK);
+    const rtnw::DeepTest real = [&](int x, int y) { return rtnw::deep_pixel(L, &cam, x, y, 40, 24); };
+    int nreal = 0;
+    for (int y = 0; y < 24; y++)
+        for (int x = 0; x < 40; x++) nreal += real(x, y);
+    EXPECT(nreal > 0 && nreal < 40 * 24);
+    tile_order({{0, 0, 40, 24}}, 40, 24, real);
+    tile_order({{0, 0, 17, 24}, {17, 0, 23, 24}}, 40, 24, real);
+    if (d) rt_scene_desc_free(d);
+    // tiles that are empty or leave the image
+    std::vector<uint32_t> xy, oi;
+    uint32_t nd = 0;
+    const int32_t bad[][4] = {{0, 0, 0, 4}, {0, 0, 4, 0}, {-1, 0, 4, 4}, {0, -1, 4, 4}, {30, 0, 11, 4}, {0, 20, 4, 5},
+                              {40, 0, 1, 1}, {1, 0, 2147483647, 1}, {2147483647, 0, 1, 1}};
+    for (const auto &t : bad) EXPECT(rtnw::tile_job_order(t, 1, 40, 24, rtnw::DeepTest(), &xy, &oi, &nd) == RT_ERR_INVALID);
+    const int32_t ok[4] = {0, 0, 4, 4};
+    EXPECT(rtnw::tile_job_order(ok, 1, 65536, 24, rtnw::DeepTest(), &xy, &oi, &nd) == RT_ERR_INVALID);
+    EXPECT(rtnw::tile_job_order(ok, 1, 40, 24, rtnw::DeepTest(), &xy, &oi, &nd) == RT_OK && xy.size() == 16);
+}
+
+// Where a frame's pixel comes in the adaptive sweep: (block row, block column, column, row).
+uint64_t sweep_key(uint32_t slot, int w) {
+    const uint32_t xx = slot % (uint32_t)w, yy = slot / (uint32_t)w;
+    return ((uint64_t)(yy / 8) << 48) | ((uint64_t)(xx / 8) << 32) | ((uint64_t)xx << 16) | yy;
+}
+
+void active_orders() {
+    const int frames[][2] = {{1, 1}, {8, 8}, {9, 17}, {40, 24}};
+    const int x0 = 5, y0 = 3;
+    for (const auto &fr : frames) {
+        const int w = fr[0], h = fr[1];
+        const uint32_t npix = (uint32_t)w * (uint32_t)h;
+        std::vector<uint8_t> deep(npix);
+        for (uint32_t o = 0; o < npix; o++) deep[o] = (o % (uint32_t)w) * 2 + (o / (uint32_t)w) < (uint32_t)w;
+        for (int pattern = 0; pattern < 4; pattern++)
+            for (int with_deep = 0; with_deep < 2; with_deep++) {
+                std::vector<uint8_t> flags(npix);
+                uint32_t lcg = 12345u + (uint32_t)pattern;
+                uint32_t nactive = 0;
+                for (uint32_t o = 0; o < npix; o++) {
+                    lcg = lcg * 1664525u + 1013904223u;
+                    flags[o] = pattern == 0 ? 1 : pattern == 1 ? 0 : pattern == 2 ? ((o % (uint32_t)w + o / (uint32_t)w) & 1) : (lcg >> 24) & 1;
+                    nactive += flags[o];
+                }
+                rtnw::ActiveJobState st;   // reused over two passes, as a frame does
+                if (with_deep) st.deep = deep;
+                std::vector<uint32_t> xy(npix + 1, 0), slot(npix + 1, 0);
+                for (int pass = 0; pass < 2; pass++) {
+                    uint32_t nd = 99;
+                    EXPECT(rtnw::active_job_order("t", flags.data(), x0, y0, w, h, nactive, &st, xy.data(), slot.data(), &nd) == RT_OK);
+                    std::vector<char> seen(npix, 0);
+                    uint32_t want_deep = 0;
+                    for (uint32_t o = 0; o < npix; o++) want_deep += with_deep && flags[o] && deep[o];
+                    EXPECT(nd == want_deep);
+                    for (uint32_t k = 0; k < nactive; k++) {
+                        const uint32_t o = slot[k];
+                        EXPECT(o < npix && flags[o] && !seen[o]);
+                        if (o >= npix) return;
+                        seen[o] = 1;
+                        EXPECT(xy[k] == ((uint32_t)(x0 + (int)(o % (uint32_t)w)) | ((uint32_t)(y0 + (int)(o / (uint32_t)w)) << 16)));
+                        if (with_deep) EXPECT((deep[o] != 0) == (k < nd));
+                        if (k && k != nd) EXPECT(sweep_key(slot[k - 1], w) < sweep_key(o, w));
+                    }
+                }
+                // a count that is not the flags' own
+                uint32_t nd = 0;
+                EXPECT(rtnw::active_job_order("t", flags.data(), x0, y0, w, h, nactive + 1, &st, xy.data(), slot.data(), &nd) ==
+                       RT_ERR_HIP);
+                EXPECT(std::strstr(rt_last_error(), "disagree") != nullptr);
+            }
+    }
+}
+
+// rt_kernel.hip refill: claim k of a launch covers [base, end) — restated here.
+void claim_range(const rtnw::BatchLaunch &l, uint64_t k, uint64_t *base, uint64_t *end) {
+    const uint64_t big = std::min<uint64_t>(k, l.nbig);
+    const uint64_t b64 = big * l.claim + (k - big) * l.claim_tail;
+    *base = std::min<uint64_t>(b64, l.nitems);
+    *end = std::min<uint64_t>(*base + (k < l.nbig ? l.claim : l.claim_tail), l.nitems);
+}
+
+void batch_checks(const rtnw::BatchPlan &pl, uint64_t b, uint64_t npix, int spp, int chunk, uint64_t waves, uint32_t ndeep,
+                  int claim_x64, int tail_claims, uint64_t *s_end) {
+    const uint32_t off = 1000u;
+    const rtnw::BatchLaunch l = rtnw::plan_batch(pl, b, npix, spp, chunk, off, waves, ndeep, claim_x64, tail_claims);
+    EXPECT(l.ns >= 1 && l.nchunks >= 1 && (uint64_t)l.nchunks <= pl.per);
+    EXPECT(((uint64_t)l.ns + chunk - 1) / chunk == (uint64_t)l.nchunks);
+    EXPECT(l.sample_offset == off + (uint32_t)(b * pl.per * (uint64_t)chunk));   // contiguous: where the previous ended
+    if (s_end) {
+        EXPECT(*s_end == b * pl.per * (uint64_t)chunk);
+        *s_end += (uint64_t)l.ns;
+    }
+    const uint64_t nitems = npix * (uint64_t)l.nchunks;
+    EXPECT(nitems <= 0xFFFFFFFFull - 64 && l.nitems == nitems);
+    EXPECT(l.ndeep_items == (uint64_t)ndeep * (uint64_t)l.nchunks);
+    if (claim_x64 < 0) EXPECT(l.claim >= 64 && l.claim <= 512 && l.claim % 64 == 0);
+    else EXPECT(l.claim == (uint64_t)std::max(1, claim_x64) * 64);
+    EXPECT(l.claim_tail == 64);
+    // every item is in exactly one claim: the big claims end inside the launch, the tail claims
+    // go on from there without a gap, and a 32-bit base + size does not wrap
+    const uint64_t big_end = (uint64_t)l.nbig * l.claim;
+    EXPECT(big_end <= nitems);
+    const uint64_t ntail = (nitems - big_end + l.claim_tail - 1) / l.claim_tail;
+    EXPECT(big_end + ntail * l.claim_tail >= nitems);
+    EXPECT((uint64_t)l.nbig + ntail + 4096 * 2 < 0xFFFFFFFFull);   // the claim counter, with every wave's last look
+    const uint64_t ks[] = {0, 1, l.nbig ? l.nbig - 1 : 0, l.nbig, l.nbig + 1, l.nbig + ntail - 1, l.nbig + ntail};
+    for (uint64_t k : ks) {
+        uint64_t b0, e0, b1, e1;
+        claim_range(l, k, &b0, &e0);
+        claim_range(l, k + 1, &b1, &e1);
+        EXPECT(e0 == b1 || (b0 == nitems && b1 == nitems));
+        EXPECT(b0 + std::max<uint32_t>(l.claim, l.claim_tail) <= 0xFFFFFFFFull || k >= l.nbig);
+        EXPECT(b0 + l.claim_tail <= 0xFFFFFFFFull);
+        if (k == 0) EXPECT(b0 == 0);
+        EXPECT(k < l.nbig + ntail ? b0 < nitems : b0 == nitems);   // nbig + ntail claims, none empty
+    }
+}
+
+void batch_plans() {
+    const uint64_t npixs[] = {1, 63, 64, 65, 250000, 1000000, 65535ull * 65535ull, 0xFFFFFFFFull - 64, 0xFFFFFFFFull - 63};
+    const int spps[] = {1, 2, 7, 1000, 2147483647}, chunks[] = {1, 2, 16, 2147483647};
+    const uint64_t waves_[] = {1, 64, 4096};
+    const int overrides[][2] = {{-1, -1}, {1, 0}, {8, 4}, {1000, -1}};
+    for (uint64_t npix : npixs)
+        for (int spp : spps)
+            for (int chunk : chunks)
+                for (uint64_t budget : {(uint64_t)1, (uint64_t)12, npix * 12 * 2, (uint64_t)16 << 30}) {
+                    rtnw::BatchPlan pl{};
+                    const int rc = rtnw::plan_batches(npix, spp, chunk, budget, 12, &pl);
+                    if (npix > 0xFFFFFFFFull - 64) {
+                        EXPECT(rc == RT_ERR_INVALID && std::strstr(rt_last_error(), "job too large") != nullptr);
+                        continue;
+                    }
+                    EXPECT(rc == RT_OK);
+                    EXPECT(pl.nchunks_total == ((uint64_t)spp + chunk - 1) / chunk);
+                    EXPECT(pl.per >= 1 && pl.nbatches >= 1);
+                    EXPECT(pl.nbatches * pl.per >= pl.nchunks_total && pl.nchunks_total > (pl.nbatches - 1) * pl.per);
+                    EXPECT((pl.per - 1) * pl.nbatches < pl.nchunks_total);   // equalised: no smaller per does it in as many
+                    EXPECT(npix * pl.per <= 0xFFFFFFFFull - 64);
+                    // within the budget unless one chunk of every pixel is already over it
+                    EXPECT(npix * pl.per * 12 <= budget || pl.per == 1);
+                    const uint32_t ndeep = (uint32_t)(npix / 3);
+                    for (uint64_t waves : waves_)
+                        for (const auto &ov : overrides) {
+                            if (pl.nbatches <= 64) {   // every batch: the samples add up
+                                uint64_t s_end = 0;
+                                for (uint64_t b = 0; b < pl.nbatches; b++)
+                                    batch_checks(pl, b, npix, spp, chunk, waves, ndeep, ov[0], ov[1], &s_end);
+                                EXPECT(s_end == (uint64_t)spp);
+                            } else {                   // both ends and the middle; the offsets tie them together
+                                for (uint64_t b : {(uint64_t)0, (uint64_t)1, pl.nbatches / 2, pl.nbatches - 2, pl.nbatches - 1})
+                                    batch_checks(pl, b, npix, spp, chunk, waves, ndeep, ov[0], ov[1], nullptr);
+                                const rtnw::BatchLaunch last =
+                                    rtnw::plan_batch(pl, pl.nbatches - 1, npix, spp, chunk, 0, waves, ndeep, ov[0], ov[1]);
+                                EXPECT((uint64_t)last.sample_offset + (uint64_t)last.ns == (uint64_t)spp);
+                            }
+                        }
+                }
+    // the feature pass: whole samples within the slab, fewer than 2^31 items per launch
+    for (uint64_t npix : {(uint64_t)1, (uint64_t)65, (uint64_t)250000, (uint64_t)0x7FFFFFFF, (uint64_t)65535 * 65535})
+        for (int spp : spps) {
+            uint64_t per = 0;
+            const int rc = rtnw::plan_feature_batches(npix, spp, 32, 256ull << 20, &per);
+            if (npix > 0x7FFFFFFFull) { EXPECT(rc == RT_ERR_INVALID); continue; }
+            EXPECT(rc == RT_OK && per >= 1 && per <= (uint64_t)spp && npix * per < 0x80000000ull);
+            EXPECT(npix * per * 32 <= (256ull << 20) || per == 1);
+        }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -232,6 +488,9 @@ int main(int argc, char **argv) {
     scenes();
     if (argc > 1) png(argv[1]);
     abi_helpers();
+    tile_orders();
+    active_orders();
+    batch_plans();
     std::printf(failures ? "FAILED %d\n" : "OK\n", failures);
     return failures ? 1 : 0;
 }
