@@ -172,8 +172,17 @@ enum {
     RT_FLAG_RIGHT_FOLD = 16
 };
 
+/* Limits, checked by every render entry point with its other arguments (RT_ERR_INVALID, the
+ * output untouched):
+ *   nx, ny          1..65535 each.  A tile may lie anywhere inside the frame; the pixel key of
+ *                   (x, j) is the uint32_t j * nx + x, below 2^32 for every such frame.
+ *   sample range    spp >= 1 and (uint64_t)sample_offset + spp <= 0xFFFFFFFF: sample indices
+ *                   are 32-bit, and the count sample_offset + spp, the mean's divisor under
+ *                   RT_FLAG_SUM_IN, is a uint32_t too.
+ *   chunk           any positive int32 (larger than spp: one work item per pixel); <= 0 selects 1.
+ *   seed            any uint64_t. */
 typedef struct rt_render_params {
-    int32_t nx, ny;               /* full image (u,v normalisation and pixel keys) */
+    int32_t nx, ny;               /* full image (u,v normalisation and pixel keys), 1..65535 each */
     int32_t spp;                  /* samples per pixel (main.cpp:251 ns) */
     int32_t max_depth;            /* scatter while depth < max_depth (main.cpp:34: 50) */
     float t_min;                  /* main.cpp:27: 0.001 */
@@ -186,7 +195,7 @@ typedef struct rt_render_params {
                                      to a per-pixel running sum in sample order: the image does
                                      not depend on the job's size or split (any rank count) */
     int32_t flags;                /* RT_FLAG_* */
-    uint32_t sample_offset;       /* first sample index (progressive rendering) */
+    uint32_t sample_offset;       /* first sample index (progressive rendering); sample_offset + spp <= 0xFFFFFFFF */
     uint32_t pad;
     uint64_t seed;                /* counter-RNG key */
 } rt_render_params;
@@ -443,7 +452,8 @@ int64_t rt_rank_pixels(int nx, int ny, int rank, int world, int32_t *tiles, int6
  *   RT_LAYOUT_LATTICE      the blocks on the interleave's a x b lattice, row-major.
  * The pixels come as 1x1 tiles in claim order (each block column by column).  Returns the
  * count (tiles == NULL: count only), RT_ERR_INVALID for a bad argument or a short buffer;
- * block <= 0 means RT_LAYOUT_BLOCK.  Replaces main.cpp:299-300's one pixel loop per job. */
+ * block <= 0 means RT_LAYOUT_BLOCK, a block above 65535 (no frame is larger) is
+ * RT_ERR_INVALID.  Replaces main.cpp:299-300's one pixel loop per job. */
 #define RT_LAYOUT_BLOCKS 0
 #define RT_LAYOUT_INTERLEAVED 1
 #define RT_LAYOUT_LATTICE 2

@@ -162,6 +162,9 @@ def lib():
         L.oracle_medium_draw.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int]
         L.oracle_medium_draw.restype = ctypes.c_double
+        L.oracle_render_axis.argtypes = [ctypes.POINTER(OracleParams), ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.POINTER(OracleStats)]
+        L.oracle_render_axis.restype = ctypes.c_int
         L.oracle_scene_dump.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_long]
         L.oracle_set_image.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.oracle_scene_dump.restype = ctypes.c_long
@@ -200,8 +203,10 @@ class RenderSpec:
                 self.background or d["background"], self.camera or d["camera"])
 
 
-def render(spec: RenderSpec):
-    """Returns (mean float32 array [h, w, 3], stats dict)."""
+def render(spec: RenderSpec, axis=None):
+    """Returns (mean float32 array [h, w, 3], stats dict).  axis: a uint8 array [h, w] that
+    receives 1 where a pixel's paths traced a ray with a direction component of exactly 0
+    (oracle_render_axis)."""
     if spec.scene == "earth":
         load_earth_image()
     depth, bg, cam = spec.resolved()
@@ -213,7 +218,10 @@ def render(spec: RenderSpec):
                      threads=spec.threads, sample_offset=spec.sample_offset, seed=spec.seed)
     out = np.zeros((h, w, 3), dtype=np.float32)
     st = OracleStats()
-    rc = lib().oracle_render(ctypes.byref(p), out.ctypes.data, ctypes.byref(st))
+    if axis is not None:
+        assert axis.dtype == np.uint8 and axis.shape == (h, w) and axis.flags.c_contiguous
+    rc = lib().oracle_render_axis(ctypes.byref(p), out.ctypes.data, None if axis is None else axis.ctypes.data,
+                                  ctypes.byref(st))
     if rc != 0:
         raise RuntimeError(f"oracle_render failed: {rc}")
     return out, {"samples": st.samples, "segments": st.segments, "seconds": st.seconds}

@@ -834,11 +834,13 @@ typedef struct {
     const scene_t *sc;
     const oracle_params *p;
     double segments;
+    double axis_rays;   /* rays with a direction component of exactly 0 (oracle_render_axis) */
 } run_t;
 
 static int world_hit(run_t *rn, const ray_t *r, hit_t *rec, rng_t *g, int depth) {
     hctx_t cx = { g, depth, rn->p->media_after };
     rn->segments += 1;
+    rn->axis_rays += r->B.e[0] == 0 || r->B.e[1] == 0 || r->B.e[2] == 0;
     int hit = obj_hit(rn->sc->world, r, rn->p->tmin, RT_MAXFLOAT, rec, &cx);
     if (rn->p->media_after) {               /* kernel order: media after the surface pass */
         float closest = hit ? rec->t : RT_MAXFLOAT;
@@ -907,7 +909,8 @@ static v3 render_pixel(run_t *rn, const cam_t *cam, int i, int j, rng_t *g) {
     v3 col = V(0, 0, 0), part = V(0, 0, 0);
     for (int s = 0; s < p->ns; s++) {
         if (g->counter) {
-            rng_seed_sample(g, sample_key(p->seed, (uint32_t)(j * p->nx + i), (uint32_t)s + p->sample_offset));
+            /* the pixel key in uint32_t: j * nx passes INT_MAX in the upper half of a 65535-wide frame */
+            rng_seed_sample(g, sample_key(p->seed, (uint32_t)j * (uint32_t)p->nx + (uint32_t)i, (uint32_t)s + p->sample_offset));
             g->nmedia = rn->sc->nmedia;
         }
         float u = (float)(i + rng_next(g)) / (float)p->nx;                /* main.cpp:305-306 */
@@ -925,7 +928,7 @@ static v3 render_pixel(run_t *rn, const cam_t *cam, int i, int j, rng_t *g) {
 /* The pixel loops over a built scene: oracle_render (a built-in scene, a preset camera) and
  * oracle_render_desc (both as given) share them. */
 static int render_scene(const scene_t *scp, const cam_t *camp, const rng_t *g_canon_p, const oracle_params *p, float *out,
-                        oracle_stats *stats) {
+                        uint8_t *axis, oracle_stats *stats) {
     const scene_t sc = *scp;
     const cam_t cam = *camp;
     int x0 = p->x0, y0 = p->y0, w = p->w, h = p->h;
@@ -938,30 +941,34 @@ static int render_scene(const scene_t *scp, const cam_t *camp, const rng_t *g_ca
     if (p->rng == 0) {
         /* canonical stream: the whole image in reference order (main.cpp:299-304) */
         rng_t g = *g_canon_p;
-        run_t rn = { &sc, p, 0 };
+        run_t rn = { &sc, p, 0, 0 };
         for (int j = p->ny - 1; j >= 0; j--) {
             for (int i = 0; i < p->nx; i++) {
+                const double a0 = rn.axis_rays;
                 v3 c = render_pixel(&rn, &cam, i, j, &g);
                 int row = p->ny - 1 - j;
                 if (row >= y0 && row < y0 + h && i >= x0 && i < x0 + w) {
                     float *o = &out[((size_t)(row - y0) * w + (i - x0)) * 3];
                     o[0] = c.e[0]; o[1] = c.e[1]; o[2] = c.e[2];
+                    if (axis) axis[(size_t)(row - y0) * w + (i - x0)] = rn.axis_rays > a0;
                 }
             }
         }
         segments = rn.segments;
     } else {
         int nt = p->threads > 0 ? p->threads : 1;
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nt) reduction(+ : segments)
-        for (int row = y0; row < y0 + h; row++) {
+        /* the pixels are shared out in runs of 64 of the rectangle's row-major order, so that a
+         * strip of one row is spread over the threads as well; every sample seeds its own stream */
+        const long npix = (long)w * h;
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nt) reduction(+ : segments)
+        for (long q = 0; q < npix; q++) {
             rng_t g; memset(&g, 0, sizeof g); g.counter = 1;
-            run_t rn = { &sc, p, 0 };
-            int j = p->ny - 1 - row;
-            for (int i = x0; i < x0 + w; i++) {
-                v3 c = render_pixel(&rn, &cam, i, j, &g);
-                float *o = &out[((size_t)(row - y0) * w + (i - x0)) * 3];
-                o[0] = c.e[0]; o[1] = c.e[1]; o[2] = c.e[2];
-            }
+            run_t rn = { &sc, p, 0, 0 };
+            const int row = y0 + (int)(q / w), i = x0 + (int)(q % w), j = p->ny - 1 - row;
+            v3 c = render_pixel(&rn, &cam, i, j, &g);
+            float *o = &out[(size_t)q * 3];
+            o[0] = c.e[0]; o[1] = c.e[1]; o[2] = c.e[2];
+            if (axis) axis[q] = rn.axis_rays > 0;
             segments += rn.segments;
         }
     }
@@ -975,15 +982,19 @@ static int render_scene(const scene_t *scp, const cam_t *camp, const rng_t *g_ca
     return 0;
 }
 
-int oracle_render(const oracle_params *p, float *out, oracle_stats *stats) {
+int oracle_render_axis(const oracle_params *p, float *out, uint8_t *axis, oracle_stats *stats) {
     scene_t sc;
     if (p->nx <= 0 || p->ny <= 0 || p->ns <= 0) return -1;
     rng_t g_canon;
     if (scene_build(&sc, p->scene, &g_canon) != 0) return -2;
     cam_t cam = camera_preset(p->camera, p->nx, p->ny);
-    int rc = render_scene(&sc, &cam, &g_canon, p, out, stats);
+    int rc = render_scene(&sc, &cam, &g_canon, p, out, axis, stats);
     scene_free(&sc);
     return rc;
+}
+
+int oracle_render(const oracle_params *p, float *out, oracle_stats *stats) {
+    return oracle_render_axis(p, out, NULL, stats);
 }
 
 /* ------------------------------------------------ scenes from a descriptor
@@ -1133,7 +1144,7 @@ int oracle_render_desc(const rt_scene_desc *d, const rt_camera_desc *c, const or
     scene_t sc;
     if (scene_from_desc(&sc, d) != 0) { scene_free(&sc); return -2; }
     cam_t cam = camera_from_desc(c);
-    int rc = render_scene(&sc, &cam, NULL, p, out, stats);
+    int rc = render_scene(&sc, &cam, NULL, p, out, NULL, stats);
     scene_free(&sc);
     return rc;
 }
@@ -1163,7 +1174,7 @@ int oracle_first_hits_desc(const rt_scene_desc *d, const rt_camera_desc *c, cons
         int j = p->ny - 1 - row;
         for (int i = x0; i < x0 + w; i++) {
             for (int s = 0; s < p->ns; s++) {
-                rng_seed_sample(&g, sample_key(p->seed, (uint32_t)(j * p->nx + i), (uint32_t)s + p->sample_offset));
+                rng_seed_sample(&g, sample_key(p->seed, (uint32_t)j * (uint32_t)p->nx + (uint32_t)i, (uint32_t)s + p->sample_offset));
                 float u = (float)(i + rng_next(&g)) / (float)p->nx;
                 float v = (float)(j + rng_next(&g)) / (float)p->ny;
                 ray_t r = camera_get_ray(&cam, u, v, &g);

@@ -112,6 +112,11 @@ void oracle_drand48(uint64_t x0, int n, double *out);
 void oracle_counter_draws(uint64_t seed, uint32_t pixel, uint32_t sample, int n, double *out);
 double oracle_medium_draw(uint64_t seed, uint32_t pixel, uint32_t sample, int bounce, int medium, int nmedia);
 
+/* oracle_render that also marks, in axis[h * w] (may be NULL), the pixels one of whose rays, at
+ * any bounce, had a direction component of exactly 0 (an axis-parallel ray: a rect's hit divides
+ * by that component).  The parity tests use the mask to leave such pixels out of a comparison. */
+int oracle_render_axis(const oracle_params *p, float *out_mean, uint8_t *axis, oracle_stats *stats);
+
 /* Texels for earth()'s image_texture, as stbi_load returned them (main.cpp:93).
  * The oracle keeps a copy; nn is the file's channel count (the texture reads stride 3). */
 void oracle_set_image(const uint8_t *data, int nx, int ny, int nn);

@@ -22,7 +22,7 @@ namespace {
 // jitters, the lens disk's candidates (two draws each, until one is accepted) and the time.
 __device__ __forceinline__ Ray camera_ray(const RtKernelArgs &A, int x, int j, uint32_t sample, uint64_t skey) {
     Rng g;
-    g.start(sample_key(skey, (uint32_t)(j * A.nx + x), sample), false);
+    g.start(sample_key(skey, (uint32_t)j * (uint32_t)A.nx + (uint32_t)x, sample), false);   // uint32_t: no signed overflow
     const float cu = div_rn((float)((double)x + g.next()), (float)A.nx, A.rnx);   // main.cpp:305-306
     const float cv = div_rn((float)((double)j + g.next()), (float)A.ny, A.rny);
     V3 disk;

@@ -329,7 +329,8 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
             pre_cp[lane] = make_uint2(c, pj);
             const uint32_t xy = A.job_xy[pj];
             const int x = (int)(xy & 0xFFFFu), j = A.ny - 1 - (int)(xy >> 16);
-            const uint64_t K = sample_key(skey, (uint32_t)(j * A.nx + x), c * (uint32_t)A.chunk + A.sample_offset);
+            // the pixel key in uint32_t: j * nx passes INT_MAX in the upper half of a 65535-wide frame
+            const uint64_t K = sample_key(skey, (uint32_t)j * (uint32_t)A.nx + (uint32_t)x, c * (uint32_t)A.chunk + A.sample_offset);
             // main.cpp:305-306; A.rnx = RN(1/float(nx)) from the host (div_rn)
             const uint64_t x1 = lcg_step(K & kLcgM), x2 = lcg_step(x1);   // the sample's first two draws
             const float cu = div_rn((float)((double)x + u48x(x1)), (float)A.nx, A.rnx);
@@ -521,7 +522,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                 const uint32_t c = item / A.npix;
                 const uint32_t xy = A.job_xy[item - c * A.npix];
                 const int px = (int)(xy & 0xFFFFu), j = A.ny - 1 - (int)(xy >> 16);
-                g.start(sample_key(skey, (uint32_t)(j * A.nx + px), (uint32_t)s_cur + A.sample_offset), kMedia);
+                g.start(sample_key(skey, (uint32_t)j * (uint32_t)A.nx + (uint32_t)px, (uint32_t)s_cur + A.sample_offset), kMedia);
                 cu_ = div_rn((float)((double)px + g.next()), (float)A.nx, A.rnx);
                 cv_ = div_rn((float)((double)j + g.next()), (float)A.ny, A.rny);
             }

@@ -38,6 +38,7 @@ static int render_adaptive(const char *fn, rt_scene *s, const rt_camera_desc *ca
     if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE | RT_FLAG_SUM_IN | RT_FLAG_SUM_OUT))
         return fail(RT_ERR_INVALID, f + ": RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
     if (w <= 0 || h <= 0 || (uint64_t)w * (uint64_t)h > 0x7FFFFFFFull) return fail(RT_ERR_INVALID, f + ": empty or oversized frame");
+    if (p->nx > 65535 || p->ny > 65535) return fail(RT_ERR_INVALID, f + ": nx and ny must be in 1..65535");
     if (guarded && (guard_radius < 0 || guard_radius > 8)) return fail(RT_ERR_INVALID, f + ": guard_radius must be in 0..8");
     if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
     if (!rt_moments_launch.resolve)

@@ -21,6 +21,8 @@ static int features_check(const char *fn, const rt_scene *s, const rt_camera_des
     if (p->nx < 1 || p->ny < 1 || p->nx > 65535 || p->ny > 65535)
         return fail(RT_ERR_INVALID, f + ": nx and ny must be in 1..65535");
     if (p->spp < 1) return fail(RT_ERR_INVALID, f + ": spp must be at least 1");
+    if (!rtnw::sample_range_ok(p->sample_offset, p->spp))
+        return fail(RT_ERR_INVALID, f + ": sample_offset + spp must not pass 0xFFFFFFFF (32-bit sample indices)");
     if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE | RT_FLAG_SUM_IN | RT_FLAG_SUM_OUT))
         return fail(RT_ERR_INVALID, f + ": RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
     if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > p->nx - w || y0 > p->ny - h)

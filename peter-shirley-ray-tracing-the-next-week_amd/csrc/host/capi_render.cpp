@@ -263,11 +263,21 @@ bool deep_first(const rt_scene *s) {
     return v;
 }
 
+// The limits of rt_render_params (rt_hip.h), held by every render entry point with its other
+// arguments, before any HIP call.
+int render_params_check(const rt_render_params *p) {
+    if (p->nx <= 0 || p->ny <= 0 || p->spp <= 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "bad render parameters");
+    if (p->nx > 65535 || p->ny > 65535) return fail(RT_ERR_INVALID, "nx and ny must be in 1..65535");
+    if (!rtnw::sample_range_ok(p->sample_offset, p->spp))
+        return fail(RT_ERR_INVALID, "sample_offset + spp must not pass 0xFFFFFFFF (32-bit sample indices)");
+    return RT_OK;
+}
+
 // The body of rt_render_tiles and rt_render_tiles_moments: the job is the tile list, or `js`
 // when non-null; with mom_dev the resolve is rt_moments.hip's, which also keeps the moments.
 int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
                const JobSlots *js, float *out_dev, float *mom_dev, void *stream_v, rt_stats *stats) {
-    if (p->nx <= 0 || p->ny <= 0 || p->spp <= 0 || p->max_depth < 0) return fail(RT_ERR_INVALID, "bad render parameters");
+    if (int rc = render_params_check(p)) return rc;
     if (s->has_moving && (cam->time0 < s->time0 || cam->time1 > s->time1))
         return fail(RT_ERR_INVALID, "camera shutter outside the scene's time span (moving-sphere bounds)");
     // RT_FLAG_RIGHT_FOLD (rt_hip.h): plain renders of width-2 scenes only, and a stack of
@@ -420,6 +430,7 @@ extern "C" {
 int rt_render_tiles(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
                     float *out_dev, void *stream_v, rt_stats *stats) {
     if (!s || !cam || !p || ntiles < 0) return fail(RT_ERR_INVALID, "rt_render_tiles: bad argument");
+    if (int rc = render_params_check(p)) return rc;   // a rank with no tiles answers as the others do
     if (ntiles == 0) {   // a rank with no tiles (more ranks than tiles) has nothing to do
         if (stats) std::memset(stats, 0, sizeof *stats);
         return RT_OK;
@@ -434,6 +445,7 @@ int rt_render_tiles_moments(rt_scene *s, const rt_camera_desc *cam, const rt_ren
     if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE))
         return fail(RT_ERR_INVALID, "rt_render_tiles_moments: RT_FLAG_COUNT and RT_FLAG_PROFILE are not supported");
     if (!s) return fail(RT_ERR_INVALID, "rt_render_tiles_moments: null scene");
+    if (int rc = render_params_check(p)) return rc;
     if (!rt_moments_launch.resolve)
         return fail(RT_ERR_UNSUPPORTED, "rt_render_tiles_moments: this library was linked without the moments unit (rt_moments.o)");
     if (ntiles == 0) {
@@ -446,7 +458,8 @@ int rt_render_tiles_moments(rt_scene *s, const rt_camera_desc *cam, const rt_ren
 
 int rt_render_tile(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
                    float *out_rgb, rt_stats *stats) {
-    if (!s || !out_rgb) return fail(RT_ERR_INVALID, "rt_render_tile: bad argument");
+    if (!s || !out_rgb || !cam || !p) return fail(RT_ERR_INVALID, "rt_render_tile: bad argument");
+    if (int rc = render_params_check(p)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     if (w <= 0 || h <= 0) return fail(RT_ERR_INVALID, "empty tile");

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "rt_hip.h"
+#include "job_plan.h"
 
 // error plumbing shared with capi_util.cpp (thread-local message)
 int rt_internal_fail(int code, const std::string &msg);
@@ -159,9 +160,11 @@ static void emit_block(int nx, int ny, int x0, int y0, int block, int32_t *tiles
 int64_t rt_rank_tiles(int nx, int ny, int rank, int world, int layout, int block, int32_t *tiles, int64_t cap) {
     if (nx <= 0 || ny <= 0 || world < 1 || rank < 0 || rank >= world || nx > 65535 || ny > 65535)
         return fail(RT_ERR_INVALID, "rt_rank_tiles: bad argument");
+    if (block <= 0) block = RT_LAYOUT_BLOCK;
+    // no frame is larger than 65535: a larger block would only overflow nx + block - 1 below
+    if (block > 65535) return fail(RT_ERR_INVALID, "rt_rank_tiles: block must not pass 65535");
     if (layout == RT_LAYOUT_INTERLEAVED) return rt_rank_pixels(nx, ny, rank, world, tiles, cap);
     if (layout != RT_LAYOUT_BLOCKS && layout != RT_LAYOUT_LATTICE) return fail(RT_ERR_INVALID, "rt_rank_tiles: unknown layout");
-    if (block <= 0) block = RT_LAYOUT_BLOCK;
     const int bx = (nx + block - 1) / block, by = (ny + block - 1) / block;
     // this rank's blocks, in claim order
     std::vector<int64_t> mine;
@@ -215,7 +218,7 @@ int rt_unpack_tiles(const float *packed, const int32_t *tiles, int64_t ntiles, i
 
 int rt_dist_render(rt_dist *d, rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, float *image,
                    rt_stats *stats) {
-    // Argument errors below depend only on (nx, ny, world, flags), which every rank of
+    // Argument errors below depend only on (nx, ny, world, flags, the sample range), which every rank of
     // one job passes alike: all ranks return them before the gather, none is left
     // waiting in the collective.
     if (!d || !s || !cam || !p) return fail(RT_ERR_INVALID, "rt_dist_render: bad argument");
@@ -226,6 +229,10 @@ int rt_dist_render(rt_dist *d, rt_scene *s, const rt_camera_desc *cam, const rt_
     // labelled as a mean image.  Progressive multi-GPU renders use rt_render_tiles.
     if (p->flags & (RT_FLAG_SUM_IN | RT_FLAG_SUM_OUT))
         return fail(RT_ERR_INVALID, "rt_dist_render: RT_FLAG_SUM_IN / RT_FLAG_SUM_OUT are not supported (mean images only)");
+    // an illegal sample range would otherwise fail in each rank's render, after which the rank
+    // still joins the gather: refused here, no collective is started for it
+    if (!rtnw::sample_range_ok(p->sample_offset, p->spp))
+        return fail(RT_ERR_INVALID, "rt_dist_render: spp must be positive and sample_offset + spp must not pass 0xFFFFFFFF");
     if (d->rank == 0 && !image) return fail(RT_ERR_INVALID, "rt_dist_render: the root needs an image buffer");
     // every rank's pixel count, so that the gather's per-rank count (the largest) is agreed
     int64_t nmax = 0;

@@ -36,6 +36,13 @@ void fill_deep_map(const SceneInfo &s, const rt_camera_desc *cam, int x0, int y0
 int active_job_order(const std::string &who, const uint8_t *flags, int x0, int y0, int w, int h, uint32_t nactive,
                      ActiveJobState *st, uint32_t *xy, uint32_t *slot, uint32_t *ndeep);
 
+// The legal sample ranges (rt_hip.h, rt_render_params): sample indices are 32-bit, and the last
+// one, sample_offset + spp - 1, must be below 0xFFFFFFFF, so that the count sample_offset + spp
+// (the mean's divisor under RT_FLAG_SUM_IN) is a uint32_t too.
+inline bool sample_range_ok(uint32_t sample_offset, int spp) {
+    return spp > 0 && (uint64_t)sample_offset + (uint64_t)spp <= 0xFFFFFFFFull;
+}
+
 // Sample batches of a render job: `per` chunks of every pixel per launch, nbatches launches.
 struct BatchPlan {
     uint64_t per, nbatches, nchunks_total;

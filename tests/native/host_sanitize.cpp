@@ -2,7 +2,9 @@
 // builders, flattening, every BVH form, the PNG decoder, the C ABI's host-only
 // helpers and its error paths, and the lowering of every built-in scene to the image of the
 // device's arrays, whose invariants are checked here, and the job arithmetic of job_plan.cpp:
-// pixel orders, sample batches and claim sizes, as properties) in a build whose host objects carry
+// pixel orders, sample batches and claim sizes, as properties, up to the ABI's limits: tiles at the
+// far corner of a 65535 x 65535 frame, jobs that end at sample index 0xFFFFFFFE, the rank
+// split's largest block) in a build whose host objects carry
 // AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_sanitizers.py; the
 // device code object is linked in unsanitised, as the GPU sanitizer is not
 // available).  Exit 0 = every call returned as expected and no sanitizer fired.
@@ -303,6 +305,22 @@ void tile_orders() {
         tile_order({{65532, 65532, 3, 3}}, 65535, 65535, d);
     }
     tile_order({{65532, 65532, 3, 3}}, 65535, 65535, [](int x, int) { return x == 65534; });
+    // 8 x 8 tiles in the corners and at the centre of the largest frame, packed in one job: the
+    // coordinates round-trip through x | y << 16 (tile_order compares every entry with its tile's)
+    const std::vector<Tile> far = {{65527, 65527, 8, 8}, {65527, 0, 8, 8}, {0, 65527, 8, 8}, {32764, 32763, 8, 8},
+                                   {65534, 65534, 1, 1}};
+    for (const rtnw::DeepTest &d : {rtnw::DeepTest(), rtnw::DeepTest([](int x, int y) { return ((x ^ y) & 1) != 0; })})
+        tile_order(far, 65535, 65535, d);
+    {
+        std::vector<uint32_t> xy, oi;
+        uint32_t nd = 0;
+        const int32_t corner[4] = {65527, 65527, 8, 8};
+        EXPECT(rtnw::tile_job_order(corner, 1, 65535, 65535, rtnw::DeepTest(), &xy, &oi, &nd) == RT_OK && xy.size() == 64);
+        if (xy.size() == 64) {
+            EXPECT(xy.front() == (65527u | (65527u << 16)) && xy.back() == (65534u | (65534u << 16)));
+            EXPECT((int)(xy.back() & 0xFFFFu) == 65534 && (int)(xy.back() >> 16) == 65534);
+        }
+    }
     // final's own deep balls under the preset camera at 40 x 24, as prepare_job asks
     rt_scene_desc *d = nullptr;
     EXPECT(rt_builtin_scene_desc("final", &d) == RT_OK);
@@ -339,9 +357,12 @@ uint64_t sweep_key(uint32_t slot, int w) {
 
 void active_orders() {
     const int frames[][2] = {{1, 1}, {8, 8}, {9, 17}, {40, 24}};
-    const int x0 = 5, y0 = 3;
+    // the frame's origin: near the image's, and so that the frame ends at pixel (65534, 65534)
+    const int origins[][2] = {{5, 3}, {65527, 65527}};
+    for (const auto &org : origins)
     for (const auto &fr : frames) {
-        const int w = fr[0], h = fr[1];
+        const int w = fr[0], h = fr[1], x0 = org[0], y0 = org[1];
+        if (x0 + w > 65535 || y0 + h > 65535) continue;
         const uint32_t npix = (uint32_t)w * (uint32_t)h;
         std::vector<uint8_t> deep(npix);
         for (uint32_t o = 0; o < npix; o++) deep[o] = (o % (uint32_t)w) * 2 + (o / (uint32_t)w) < (uint32_t)w;
@@ -371,6 +392,8 @@ void active_orders() {
                         if (o >= npix) return;
                         seen[o] = 1;
                         EXPECT(xy[k] == ((uint32_t)(x0 + (int)(o % (uint32_t)w)) | ((uint32_t)(y0 + (int)(o / (uint32_t)w)) << 16)));
+                        // as the kernel unpacks them
+                        EXPECT((int)(xy[k] & 0xFFFFu) == x0 + (int)(o % (uint32_t)w) && (int)(xy[k] >> 16) == y0 + (int)(o / (uint32_t)w));
                         if (with_deep) EXPECT((deep[o] != 0) == (k < nd));
                         if (k && k != nd) EXPECT(sweep_key(slot[k - 1], w) < sweep_key(o, w));
                     }
@@ -480,6 +503,76 @@ void batch_plans() {
         }
 }
 
+// The sample range's rule, every batch of a job that ends at the last legal index, and the rank
+// split's block limit (include/rt_hip.h, rt_render_params and rt_rank_tiles).
+void limits() {
+    EXPECT(rtnw::sample_range_ok(0, 1) && rtnw::sample_range_ok(0, 2147483647) && rtnw::sample_range_ok(0xFFFFFFFEu, 1));
+    EXPECT(rtnw::sample_range_ok(0xFFFFFFFFu - 2147483647u, 2147483647) && rtnw::sample_range_ok(0xFFFFFFF8u, 7));
+    EXPECT(!rtnw::sample_range_ok(0xFFFFFFFFu, 1) && !rtnw::sample_range_ok(0xFFFFFFF9u, 7) && !rtnw::sample_range_ok(0xFFFFFFFEu, 7));
+    EXPECT(!rtnw::sample_range_ok(0x80000001u, 2147483647) && !rtnw::sample_range_ok(0, 0) && !rtnw::sample_range_ok(5, -1));
+    // a legal job that ends at index 0xFFFFFFFE: no batch starts below the job's offset (a wrapped
+    // sum would) or ends past 0xFFFFFFFF, each starts where the one before ended, the last at the limit
+    const uint64_t npixs[] = {1, 64, 65535, 65535ull * 65535ull};
+    const int spps[] = {1, 7, 1000, 2147483647}, chunks[] = {1, 3, 2147483647};
+    for (uint64_t npix : npixs)
+        for (int spp : spps)
+            for (int chunk : chunks)
+                for (uint64_t budget : {(uint64_t)1, npix * 12 * 2, (uint64_t)16 << 30}) {
+                    const uint32_t off = 0xFFFFFFFFu - (uint32_t)spp;
+                    EXPECT(rtnw::sample_range_ok(off, spp));
+                    rtnw::BatchPlan pl{};
+                    EXPECT(rtnw::plan_batches(npix, spp, chunk, budget, 12, &pl) == RT_OK);
+                    uint64_t want = off;
+                    std::vector<uint64_t> bs;
+                    if (pl.nbatches <= 64)
+                        for (uint64_t b = 0; b < pl.nbatches; b++) bs.push_back(b);
+                    else
+                        bs = {0, 1, pl.nbatches / 2, pl.nbatches - 2, pl.nbatches - 1};
+                    for (uint64_t b : bs) {
+                        const rtnw::BatchLaunch l = rtnw::plan_batch(pl, b, npix, spp, chunk, off, 64, 0, -1, -1);
+                        EXPECT(l.ns >= 1 && l.sample_offset >= off);
+                        EXPECT((uint64_t)l.sample_offset + (uint64_t)l.ns <= 0xFFFFFFFFull);
+                        EXPECT((uint64_t)l.sample_offset == (uint64_t)off + b * pl.per * (uint64_t)chunk);
+                        if (pl.nbatches <= 64) {
+                            EXPECT((uint64_t)l.sample_offset == want);
+                            want += (uint64_t)l.ns;
+                        }
+                        if (b + 1 == pl.nbatches) EXPECT((uint64_t)l.sample_offset + (uint64_t)l.ns == 0xFFFFFFFFull);
+                    }
+                }
+    // rt_rank_tiles: 65535 is the largest block (one block holds any frame); above it nx + block - 1
+    // would overflow for INT_MAX: refused, for every layout
+    for (int layout : {RT_LAYOUT_BLOCKS, RT_LAYOUT_INTERLEAVED, RT_LAYOUT_LATTICE}) {
+        EXPECT(rt_rank_tiles(37, 23, 0, 1, layout, 65535, nullptr, 0) == 37 * 23);
+        EXPECT(rt_rank_tiles(65535, 9, 1, 2, layout, 65535, nullptr, 0) == (layout == RT_LAYOUT_BLOCKS ? 0 : layout == RT_LAYOUT_LATTICE ? 0 : 32767 * 9));
+        for (int block : {65536, 2147483647}) {
+            EXPECT(rt_rank_tiles(37, 23, 0, 1, layout, block, nullptr, 0) == RT_ERR_INVALID);
+            EXPECT(std::strstr(rt_last_error(), "block") != nullptr);
+        }
+        // the widest frame, two block rows: the ranks' pixels partition it
+        const int nx = 65535, ny = 9, world = 3;
+        std::vector<uint8_t> seen((size_t)nx * ny, 0);
+        int64_t total = 0;
+        for (int r = 0; r < world; r++) {
+            const int64_t n = rt_rank_tiles(nx, ny, r, world, layout, 0, nullptr, 0);
+            EXPECT(n >= 0);
+            if (n < 0) continue;
+            std::vector<int32_t> t((size_t)n * 4);
+            EXPECT(rt_rank_tiles(nx, ny, r, world, layout, 0, t.data(), n) == n);
+            for (int64_t k = 0; k < n; k++) {
+                const int x = t[4 * k], y = t[4 * k + 1];
+                EXPECT(x >= 0 && x < nx && y >= 0 && y < ny && t[4 * k + 2] == 1 && t[4 * k + 3] == 1);
+                if (x >= 0 && x < nx && y >= 0 && y < ny) seen[(size_t)y * nx + x]++;
+            }
+            total += n;
+        }
+        EXPECT(total == (int64_t)nx * ny);
+        size_t once = 0;
+        for (uint8_t v : seen) once += v == 1;
+        EXPECT(once == seen.size());
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -491,6 +584,7 @@ int main(int argc, char **argv) {
     tile_orders();
     active_orders();
     batch_plans();
+    limits();
     std::printf(failures ? "FAILED %d\n" : "OK\n", failures);
     return failures ? 1 : 0;
 }

@@ -3,7 +3,8 @@
  * (tests/test_sanitizers.py): every scene, both RNG modes and both media orders, a
  * clipped output rectangle, the quantiser, the PPM writer and the RNG helpers; and the
  * descriptor entry points (oracle_render_desc, oracle_first_hits_desc) on a hand-made
- * descriptor with every primitive, texture and material kind, a 6-op chain and 70 media.
+ * descriptor with every primitive, texture and material kind, a 6-op chain and 70 media;
+ * and all three render entry points at the ABI's limits (limits_check).
  * Exit 0 = every render returned 0 and no sanitizer fired. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,6 +15,9 @@
 /* A descriptor of 5 primitives (one of each kind, two under a 6-op chain), all four texture
  * kinds, all five material kinds and 70 media over two boundary spheres each (past the 64 the
  * oracle's media list once held), rendered in both orders and in first-hit mode. */
+static rt_scene_desc g_desc;     /* desc_check's descriptor and camera, kept for limits_check */
+static rt_camera_desc g_cam;
+
 static int desc_check(void) {
     enum { NMED = 70 };
     static rt_prim prims[5], bprims[2 * NMED];
@@ -96,11 +100,49 @@ static int desc_check(void) {
     media[3].order = 3 * 6 / NMED;
     d.perlin_perm = NULL;     /* as rt_scene_create: missing Perlin tables */
     if (oracle_render_desc(&d, &c, &q, img, NULL) != -2) { printf("descriptor: missing Perlin tables were not refused\n"); bad++; }
+    d.perlin_perm = perm;
+    g_desc = d;
+    g_cam = c;
+    return bad;
+}
+
+/* The ABI's numeric limits (include/rt_hip.h): 8 x 8 tiles in the corners and at the centre of
+ * a 65535 x 65535 frame (the centre tile holds row j = 32768 and column 32768, where the pixel
+ * key j * nx + x reaches 2^31; from j = 32769 on j * nx passes INT_MAX), the last sample
+ * indices (sample_offset = 0xFFFFFFF0) and a seed of all ones, through oracle_render,
+ * oracle_render_desc and oracle_first_hits_desc. */
+static int limits_check(void) {
+    enum { N = 65535, T = 8, NS = 3 };
+    static const int at[5][2] = {{0, 0}, {N - T, 0}, {0, N - T}, {N - T, N - T}, {32764, 32763}};
+    static float img[T * T * 3], depth[T * T * NS], nrm[T * T * NS * 3], alb[T * T * NS * 3];
+    static int32_t prim[T * T * NS];
+    static uint8_t axis[T * T];
+    int bad = 0;
+    for (int t = 0; t < 5; t++)
+        for (int fold = 0; fold < 2; fold++) {
+            oracle_params p;
+            memset(&p, 0, sizeof p);
+            p.scene = ORACLE_SCENE_RANDOM; p.camera = ORACLE_CAM_RANDOM; p.background = 1;
+            p.nx = N; p.ny = N; p.ns = NS; p.max_depth = 8; p.tmin = 0.001f; p.rng = 1;
+            p.media_after = 1; p.forward = !fold; p.chunk = 2; p.threads = 2;
+            p.x0 = at[t][0]; p.y0 = at[t][1]; p.w = T; p.h = T;
+            p.sample_offset = 0xFFFFFFF0u; p.seed = ~(uint64_t)0;
+            oracle_stats st;
+            if (oracle_render_axis(&p, img, axis, &st) != 0) { printf("limits: tile %d fold %d: render failed\n", t, fold); bad++; }
+            for (int i = 0; i < T * T; i++) if (axis[i] > 1) { printf("limits: tile %d: the axis mask is not 0 or 1\n", t); bad++; break; }
+            float sum = 0;
+            for (int i = 0; i < T * T * 3; i++) sum += img[i];
+            if (!(sum > 0)) { printf("limits: tile %d fold %d: a black tile under the sky\n", t, fold); bad++; }
+            p.scene = -1; p.max_depth = 50;
+            if (oracle_render_desc(&g_desc, &g_cam, &p, img, NULL) != 0) { printf("limits: tile %d: descriptor render failed\n", t); bad++; }
+            if (oracle_first_hits_desc(&g_desc, &g_cam, &p, prim, depth, nrm, alb) != 0) { printf("limits: tile %d: first hits failed\n", t); bad++; }
+        }
     return bad;
 }
 
 int main(void) {
     int bad = desc_check();
+    bad += limits_check();
     static float img[24 * 16 * 3];
     static uint8_t rgb[24 * 16 * 3];
     static char text[24 * 16 * 16 + 64];

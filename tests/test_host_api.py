@@ -316,6 +316,46 @@ def test_block_deal_partitions_the_image():
         assert max(counts) - min(counts) <= 64
 
 
+LAYOUTS = (rtnw.RT_LAYOUT_BLOCKS, rtnw.RT_LAYOUT_INTERLEAVED, rtnw.RT_LAYOUT_LATTICE)
+
+
+def test_rank_tiles_refuses_a_block_above_65535():
+    """No frame is wider than 65535, and nx + block - 1 must not overflow an int: 65535 is the
+    largest block (one block holds any frame), 65536 and INT_MAX are RT_ERR_INVALID."""
+    L = rtnw.lib()
+    for layout in LAYOUTS:
+        for block in (65536, 2 ** 31 - 1):
+            assert L.rt_rank_tiles(37, 23, 0, 2, layout, block, None, 0) == -1   # RT_ERR_INVALID
+            assert b"block" in L.rt_last_error()
+        assert L.rt_rank_tiles(37, 23, 0, 1, layout, 65535, None, 0) == 37 * 23
+    assert L.rt_rank_tiles(65535, 9, 0, 1, rtnw.RT_LAYOUT_LATTICE, 65535, None, 0) == 65535 * 9
+
+
+def test_rank_layouts_partition_a_65535_by_9_frame():
+    """The widest frame, one block row and one pixel row more: the ranks' pixels partition it
+    exactly, for each layout."""
+    nx, ny = 65535, 9
+    for layout in LAYOUTS:
+        for world in (1, 3, 8):
+            seen = np.zeros((ny, nx), np.int32)
+            for r in range(world):
+                t = rtnw.rank_tiles_c(nx, ny, r, world, layout)
+                assert (t[:, 2:] == 1).all() and t[:, 0].min() >= 0 and t[:, 1].min() >= 0
+                np.add.at(seen, (t[:, 1], t[:, 0]), 1)
+            assert (seen == 1).all(), (layout, world)
+
+
+@pytest.mark.parametrize("dev", [False, True])
+def test_render_features_refuses_an_illegal_sample_range_before_the_device(dev):
+    """(uint64_t)sample_offset + spp <= 0xFFFFFFFF is legal, anything above RT_ERR_INVALID,
+    checked with the other arguments: a null scene is only reached by a legal range."""
+    from test_features_spec import _features
+    for total, legal in ((2 ** 32 - 1, True), (2 ** 32, False), (2 ** 32 + 5, False)):
+        rc, msg = _features(rtnw.RenderParams(4, 3, 7, seed=1, sample_offset=total - 7), dev=dev)   # offsets that fit 32 bits
+        assert rc == -1
+        assert ("null scene" in msg) if legal else ("sample_offset" in msg and "null scene" not in msg), msg
+
+
 def test_math_probe_rejects_bad_arguments():
     """rt_math_probe (the device-transcendental diagnostic) validates before touching the GPU."""
     RT_ERR_INVALID = -1   # include/rt_hip.h
