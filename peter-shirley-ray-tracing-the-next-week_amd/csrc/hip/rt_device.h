@@ -1472,6 +1472,20 @@ __device__ __forceinline__ void medium_one(const RtKernelArgs &A, const MediumRe
     med_mat = hit ? md.w : med_mat;
 }
 
+// Medium k's record from the workgroup's LDS copy (load_media), through an explicit LDS pointer:
+// three broadcast 16-B reads (media_hit, and the ball waves' fused step in rt_kernel.hip).
+__device__ __forceinline__ MediumRec lds_medium_rec(const MediumRec *lds_media, int k) {
+    typedef unsigned U4v __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) const U4v LdsU4;
+    const LdsU4 *p = (const LdsU4 *)lds_media + 3 * k;
+    const U4v x = p[0], y = p[1], z = p[2];
+    MediumRec M;
+    M.md = make_int4((int)x.x, (int)x.y, (int)x.z, (int)x.w);
+    M.g0 = make_float4(__uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(y.z), __uint_as_float(y.w));
+    M.mm = make_float4(__uint_as_float(z.x), __uint_as_float(z.y), __uint_as_float(z.z), __uint_as_float(z.w));
+    return M;
+}
+
 // All media in list order.  The first RT_LDS_MEDIA come from the workgroup's LDS
 // copy through an explicit LDS pointer, the rest from HBM, in two loops: one loop
 // choosing per medium between the two made the compiler select the address and
@@ -1481,17 +1495,10 @@ __device__ __forceinline__ int media_hit(const RtKernelArgs &A, const MediumRec 
                                          const Recip &rd, Rng &g, bool &have, float &best_t, Counters &cnt) {
     // a = |d|^2 of the boundary spheres' quadratics (sphere.h:28), its reciprocal once for all media
     const Recip ra = recip_of(dot(r.d, r.d), true);
-    typedef unsigned U4v __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) const U4v LdsU4;
     int med_mat = -1;
     const int nl = min(A.nmedia, RT_LDS_MEDIA);
     for (int k = 0; k < nl; ++k) {
-        const LdsU4 *p = (const LdsU4 *)lds_media + 3 * k;
-        const U4v x = p[0], y = p[1], z = p[2];
-        MediumRec M;
-        M.md = make_int4((int)x.x, (int)x.y, (int)x.z, (int)x.w);
-        M.g0 = make_float4(__uint_as_float(y.x), __uint_as_float(y.y), __uint_as_float(y.z), __uint_as_float(y.w));
-        M.mm = make_float4(__uint_as_float(z.x), __uint_as_float(z.y), __uint_as_float(z.z), __uint_as_float(z.w));
+        const MediumRec M = lds_medium_rec(lds_media, k);
         g.xm = lcg_step(g.xm);   // this medium's draw, taken or not
         medium_one<kCount, kInst>(A, M, k, r, rd, ra, g.xm, have, best_t, med_mat, mc, cnt);
     }

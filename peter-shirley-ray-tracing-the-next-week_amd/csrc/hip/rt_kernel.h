@@ -95,6 +95,11 @@ struct RtKernelArgs {
     // d in [0, max_depth); fold_stride = the launch's lanes (grid x block)
     float4 *fold;
     uint32_t fold_stride;
+    // the ball waves' fused in-ball step (stage 3; last, so that the other variants' argument
+    // offsets stay as they were): 0 off, else the eligible lanes a trip of its loop needs, and
+    // the media's constant albedos in list order (scene_lower.cpp ball_fast_media)
+    int ball_fast;
+    float ball_alb[2][3];
 };
 
 // mode: 0 plain, 1 count, 2 profile, RT_LAUNCH_FOLD the plain right-fold variant (width 2 only)

@@ -179,7 +179,8 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     if (kMedia) load_media<kBlock>(A, lds_media);
     if (threadIdx.x == 0) {
         lds_pool_ctl[0] = lds_pool_ctl[1] = lds_pool_ctl[2] = 0;
-        lds_pool_ctl[3] = kBall ? (uint32_t)min(max(A.ball_waves, 0), kBlock / 64) : 0u;
+        // (no medium cell: no paths for ball waves, none run)
+        lds_pool_ctl[3] = kBall && A.cell_n > 0 ? (uint32_t)min(max(A.ball_waves, 0), kBlock / 64) : 0u;
         store_camera(A, lds_cam);
         lds_mconst = LogConsts{1.0 / 7, -1.0 / 6, 0.2, -0.25, 1.0 / 3};
     }
@@ -256,6 +257,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     Counters cnt;
     uint64_t prof[5] = {0, 0, 0, 0, 0};   // claim, traverse, media, shade, of which scatter branches
     uint64_t prof_iters = 0;              // (kProf) this wave's loop iterations
+    uint64_t fast_trips = 0, fast_cycles = 0;   // (kProf) the fused in-ball step's trips and their cycles (part of traverse)
     uint64_t stamp = kProf ? __builtin_amdgcn_s_memtime() : 0;
     // wave timeline (kProf): start, first sight of the empty pool, end (s_memrealtime: one clock for all CUs)
     const uint64_t rt_start = kProf ? __builtin_amdgcn_s_memrealtime() : 0;
@@ -354,7 +356,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     // every sample's draws, adds and slab slot are its own wherever it runs: images are
     // bitwise unchanged.  One spin lock guards both pools; a wave leaves the kernel only
     // after seeing both pools empty, so no path is stranded.
-    const bool ballrole = kBall && (int)wave >= kBlock / 64 - A.ball_waves;   // wave-uniform
+    const bool ballrole = kBall && A.cell_n > 0 && (int)wave >= kBlock / 64 - A.ball_waves;   // wave-uniform
     typedef __attribute__((address_space(3))) volatile uint32_t LdsVU;
     auto pool_peek = [&](int k) -> uint32_t {   // a racy hint; decisions are made under the lock
         return __builtin_amdgcn_readfirstlane(((LdsVU *)lds_pool_ctl)[1 + k]);
@@ -385,6 +387,9 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         const uint64_t M = wballot(want);
         if (M == 0ull) return false;
         const uint32_t cap = k == 0 ? RT_BALL_POOL : RT_NORM_POOL;
+        // the last ball wave has left: nobody is coming for the ball's pool but the pusher itself
+        // (a stale read only sends a path the old way: the pusher stays until the pool is empty)
+        if (k == 0 && __builtin_amdgcn_readfirstlane(((LdsVU *)lds_pool_ctl)[3]) == 0u) return false;
         if (pool_peek(k) >= cap) {
             if (kCount && k == 0 && lane == 0) cnt.ball[RT_BALL_DENIED] += (uint64_t)__popcll(M);
             return false;
@@ -444,6 +449,20 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
             begin_segment(false);   // (the segment was counted where it began)
         }
         return got;
+    };
+
+    // (medium cell) whether the lane's ray starts inside the cell's ball, and if so tsafe: a
+    // distance safely below where it leaves the ball (stage 3's cell block and fused step)
+    auto cell_exit = [&](float &tsafe) -> bool {
+        const V3 oc = sub(r.o, mk(A.cell_c[0], A.cell_c[1], A.cell_c[2]));
+        const float a = dot(r.d, r.d), b = dot(oc, r.d), cc = dot(oc, oc) - A.cell_r2;
+        if (!(cc < 0.f && a > 0.f)) return false;
+        // where the ray leaves the ball: the larger root, without cancellation
+        // (approximate square root and reciprocals, ~1 ulp each: a bound, not a result)
+        const float q = __builtin_amdgcn_sqrtf(b * b - a * cc);
+        const float te = b >= 0.f ? -cc * __builtin_amdgcn_rcpf(b + q) : (q - b) * __builtin_amdgcn_rcpf(a);
+        tsafe = te * (1.f - 1.f / 4096);   // below it by far more than its rounding
+        return true;
     };
 
     // retire a finished work item (its sum to the slab), hand the lanes without work
@@ -665,21 +684,96 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
             // primitives near it; a hit before the ray leaves the ball is the closest of
             // all (every other primitive lies outside), and the search ends without a descent
             if (kCell && ballrole && A.cell_n > 0) {
+                // The fused in-ball step (A.ball_fast > 0).  Nearly every
+                // segment a ball wave holds starts inside the ball, is decided by the cell and
+                // scatters at a medium whose material is an isotropic of constant albedo (the
+                // host checks that of every medium: scene_lower.cpp ball_fast_media).  For such a
+                // segment stages 3-5 reduce to the cell test, the media, the sampler's point and
+                // six assignments, so a ball wave runs just that, trip after trip, while at least
+                // A.ball_fast of its lanes hold such a segment, with no claim, pool or lock.
+                // A lane whose segment turns out otherwise (a cell primitive first, the cell
+                // undecided, no scatter) is left as it was, the medium stream included, sits out
+                // the further trips and is served from scratch by the generic stages below; so is
+                // a lane at the depth cap.  A trip raises the depth of the lanes it serves and
+                // retires the others, so the loop ends after at most max_depth + 1 trips.  The
+                // expressions are the generic stages' own (lockstep_prims, medium_one,
+                // coop_reject_mixed): images are bitwise unchanged.
+                if (A.ball_fast > 0) {
+                    bool sat_out = false;
+                    for (;;) {
+                        bool el = fresh && phase == PH_TRAV && !sat_out && depth < A.max_depth;
+                        float tsafe = 0.f;
+                        if (el) el = cell_exit(tsafe);
+                        if (__popcll(wballot(el)) < A.ball_fast) break;
+                        const uint64_t t_in = kProf ? __builtin_amdgcn_s_memtime() : 0;
+                        // (kCount) a lane that is not served is counted by the generic stages alone
+                        const uint64_t c_sph = cnt.spheres, c_msp = cnt.mspheres, c_rec = cnt.rects, c_ins = cnt.instanced,
+                                       c_med = cnt.media;
+                        // a fresh segment: best_t, best_key, best_prim hold begin_segment()'s values
+                        lockstep_prims<kCount, kInst, true>((const ConstF4 *)A.prims, A.cell_first, A.cell_n, A.insts, r, A.tmin,
+                                                            el, -1, best_t, best_key, best_prim, cnt);
+                        const bool decided = el && best_t < tsafe;
+                        uint64_t xm = g.xm;
+                        int kh = -1;   // the medium that scatters, if any
+                        if (el) {      // stage 4's media_hit over the LDS records (at most 2 media here)
+                            const Recip rd = recip_of(len(r.d), true);
+                            const Recip ra = recip_of(dot(r.d, r.d), true);
+                            bool have = best_prim != 0xFFFFFFFFu;
+                            const int nl = min(A.nmedia, 2);
+                            for (int k = 0; k < nl; ++k) {
+                                const MediumRec M = lds_medium_rec(lds_media, k);
+                                xm = lcg_step(xm);
+                                int mm = -1;
+                                medium_one<kCount, kInst>(A, M, k, r, rd, ra, xm, have, best_t, mm, (LdsMediaConsts *)&lds_mconst, cnt);
+                                kh = mm >= 0 ? k : kh;
+                            }
+                        }
+                        const bool commit = decided && kh >= 0;
+                        if (kCount) {
+                            if (el && !commit) {
+                                cnt.spheres = c_sph; cnt.mspheres = c_msp; cnt.rects = c_rec; cnt.instanced = c_ins;
+                                cnt.media = c_med;
+                            }
+                            if (commit) { cnt.shades++; cnt.l_scatter++; }
+                            const uint64_t nc = wballot(commit);
+                            if (lane == 0) cnt.ball[RT_BALL_CELL_BALL] += (uint64_t)__popcll(nc);
+                        }
+                        // material.h:145-149 with the lane's own rejection loop (all 64 lanes run the rounds)
+                        const uint64_t trips0 = cnt.w_rius, local0 = cnt.w_local;   // (kCount)
+                        const V3 pt = coop_reject_mixed<kCount>(commit, false, g, slots, jt, lane, cnt, A.coop_local,
+                                                                A.coop_local_min);
+                        if (kCount && lane == 0) {
+                            const uint64_t local = cnt.w_local - local0, rounds = cnt.w_rius - trips0 - local;
+                            cnt.sampler[RT_SAMPLER_LOCAL] += local;
+                            cnt.sampler[RT_SAMPLER_ROUNDS] += rounds;
+                            cnt.sampler[RT_SAMPLER_BALL_LOCAL] += local;
+                            cnt.sampler[RT_SAMPLER_BALL_ROUNDS] += rounds;
+                        }
+                        if (commit) {
+                            g.xm = xm;
+                            r.o = at(r, best_t);
+                            r.d = pt;
+                            r.time = 0.0f;
+                            beta = mul(beta, kh == 0 ? mk(A.ball_alb[0][0], A.ball_alb[0][1], A.ball_alb[0][2])
+                                                     : mk(A.ball_alb[1][0], A.ball_alb[1][1], A.ball_alb[1][2]));
+                            ++depth;
+                            begin_segment();
+                        } else if (el) {
+                            sat_out = true;
+                            best_t = RT_FLT_MAX;
+                            best_key = 0x7FFFFFFF;
+                            best_prim = 0xFFFFFFFFu;
+                        }
+                        if (kProf) {
+                            fast_trips++;
+                            fast_cycles += __builtin_amdgcn_s_memtime() - t_in;
+                        }
+                    }
+                }
                 bool in = false;
                 float tsafe = 0.f;
                 const bool fr = fresh && phase == PH_TRAV;
-                if (fr) {
-                    const V3 oc = sub(r.o, mk(A.cell_c[0], A.cell_c[1], A.cell_c[2]));
-                    const float a = dot(r.d, r.d), b = dot(oc, r.d), cc = dot(oc, oc) - A.cell_r2;
-                    if (cc < 0.f && a > 0.f) {
-                        // where the ray leaves the ball: the larger root, without cancellation
-                        // (approximate square root and reciprocals, ~1 ulp each: a bound, not a result)
-                        const float q = __builtin_amdgcn_sqrtf(b * b - a * cc);
-                        const float te = b >= 0.f ? -cc * __builtin_amdgcn_rcpf(b + q) : (q - b) * __builtin_amdgcn_rcpf(a);
-                        tsafe = te * (1.f - 1.f / 4096);   // below it by far more than its rounding
-                        in = true;
-                    }
-                }
+                if (fr) in = cell_exit(tsafe);
                 if (wballot(in) != 0ull) {
                     lockstep_prims<kCount, kInst, true>((const ConstF4 *)A.prims, A.cell_first, A.cell_n, A.insts, r, A.tmin,
                                                         in, -1, best_t, best_key, best_prim, cnt);
@@ -895,6 +989,8 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
             if (ballrole) {
                 for (int k = 0; k < 4; ++k) atomicAdd(&A.stats[RT_STAT_BALL + k], (unsigned long long)(prof[k] + (k == 3 ? prof[4] : 0)));
                 atomicAdd(&A.stats[RT_STAT_BALL + 4], (unsigned long long)prof_iters);
+                atomicAdd(&A.stats[RT_STAT_BALL + 6], (unsigned long long)fast_trips);
+                atomicAdd(&A.stats[RT_STAT_BALL + 7], (unsigned long long)fast_cycles);
             }
             atomicAdd(&A.stats[RT_STAT_BALL + 5], (unsigned long long)prof_iters);
         }

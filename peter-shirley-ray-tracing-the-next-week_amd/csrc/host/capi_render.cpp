@@ -29,9 +29,20 @@ double algorithmic_bytes(const rt_stats &st, double items, int bvh_width) {
 // env RTNW_BALL_WAVES (0: none) for A/B runs.  Their ready batch (RTNW_BALL_BATCH) and the
 // busy lanes below which they claim new samples (RTNW_BALL_CLAIM): 56 and 48 against 48 and
 // 64, c4 48.87 -> 48.50 ms, the share of 8 25.20 -> 25.05 ms (profiles/r06/knobs3_ab.log).
-#define RT_BALL_WAVES 3
+// With the fused in-ball step below a ball wave serves about three times the segments per cycle
+// in its trips, and 2 ball waves measure faster than 3 (c4 46.35 against 46.95 ms, 4: 48.1;
+// profiles/r08/sweep.log).
+#define RT_BALL_WAVES 2
 #define RT_BALL_BATCH 56
 #define RT_BALL_CLAIM 48
+// The ball waves' fused in-ball step (rt_kernel.hip stage 3): the eligible lanes another trip of
+// its loop needs; env RTNW_BALL_FAST (0: off) for A/B runs.  Scenes whose media do not qualify
+// (scene_lower.cpp ball_fast_media) run without it whatever the setting.  A trip costs the same
+// however few lanes it serves: 40 / 48 / 56 measure alike, 16 and 64 (hardly ever reached)
+// slower than the step off (profiles/r08/sweep.log).
+#ifndef RT_BALL_FAST
+#define RT_BALL_FAST 48
+#endif
 // The shading stage's rejection sampler (rt_device.h coop_reject_mixed): candidates each
 // requesting lane tries by itself before the cooperative rounds (RTNW_COOP_LOCAL, 0: none),
 // in waves with at least RTNW_COOP_LOCAL_MIN requesters.  Any setting renders the same image;
@@ -179,9 +190,10 @@ int read_counters(rt_scene *s, bool count, bool prof, double items, rt_stats *st
             const unsigned long long *b = c + RT_STAT_BALL;
             std::fprintf(stderr,
                          "rtnw ball waves (profile): iterations %llu of %llu; cycles claim %llu of %llu, traverse %llu of "
-                         "%llu, media %llu of %llu, shade %llu of %llu\n",
+                         "%llu, media %llu of %llu, shade %llu of %llu; fused in-ball trips %llu, their cycles %llu "
+                         "(part of traverse)\n",
                          b[4], b[5], b[0], c[RT_STAT_PROF], b[1], c[RT_STAT_PROF + 1], b[2], c[RT_STAT_PROF + 2], b[3],
-                         c[RT_STAT_PROF + 3]);
+                         c[RT_STAT_PROF + 3], b[6], b[7]);
         }
         stats->cycles_claim = (double)c[RT_STAT_PROF + 0];
         stats->cycles_traverse = (double)c[RT_STAT_PROF + 1];
@@ -322,7 +334,11 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     fill_scene_args(s, a);
     fill_camera_args(cam, p, a);
     a.need_dlen = s->nmedia > 0 || s->has_specular || p->background == RT_BG_SKY;
-    a.ball_waves = ball_waves();
+    // (a scene without a medium cell has no paths for ball waves: none are made)
+    a.ball_waves = s->cell_n > 0 ? ball_waves() : 0;
+    a.ball_fast = s->ball_fast ? env_int("RTNW_BALL_FAST", RT_BALL_FAST, 0, 64) : 0;
+    for (int i = 0; i < 2; i++)
+        for (int k = 0; k < 3; k++) a.ball_alb[i][k] = s->ball_alb[i][k];
     a.ball_batch = env_int("RTNW_BALL_BATCH", RT_BALL_BATCH, 1, 64);
     a.ball_claim = env_int("RTNW_BALL_CLAIM", RT_BALL_CLAIM, 1, 64);
     a.ball_park = env_int("RTNW_BALL_PARK", 1, 0, 1);

@@ -136,4 +136,13 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out) {
     return RT_OK;
 }
 
+// Diagnostics (declared in scene_lower.h, not in rt_hip.h): whether scene lowering enables the
+// ball waves' fused in-ball step for `d` (scene_lower.cpp ball_fast_media).  Host arithmetic only.
+int rt_scene_desc_ball_fast(const rt_scene_desc *d) {
+    if (int rc = rtnw::validate_desc(d)) return rc;
+    rtnw::LoweredScene low;
+    if (int rc = rtnw::lower_scene(d, &low)) return rc;
+    return low.ball_fast ? 1 : 0;
+}
+
 }  // extern "C"

@@ -277,6 +277,23 @@ std::vector<rt_dmaterial> to_dmaterials(const rt_scene_desc *d, SceneInfo &s) {
     return mats;
 }
 
+// The ball waves' fused in-ball step (rt_kernel.hip stage 3) scatters a path at a medium without
+// the shading stage: it is enabled only where that stage would do nothing else for any medium of
+// the scene — each medium's material an isotropic whose texture is the constant resolved above
+// (flag 2; final()'s two) — and the scene has a medium cell.  The constants go to the kernel
+// arguments in list order.
+void ball_fast_media(const rt_scene_desc *d, const std::vector<rt_dmaterial> &mats, SceneInfo &s) {
+    s.ball_fast = false;
+    if (s.cell_n <= 0 || d->nmedia < 1 || d->nmedia > 2) return;
+    for (int i = 0; i < d->nmedia; i++) {
+        const int m = d->media[i].material;
+        if (m < 0 || m >= (int)mats.size() || mats[m].kind != RT_MAT_ISOTROPIC || !(mats[m].flags & 2)) return;
+    }
+    for (int i = 0; i < d->nmedia; i++)
+        for (int k = 0; k < 3; k++) s.ball_alb[i][k] = mats[d->media[i].material].albedo[k];
+    s.ball_fast = true;
+}
+
 std::vector<rt_dtexture> to_dtextures(const rt_scene_desc *d, SceneInfo &s) {
     std::vector<rt_dtexture> texs(d->ntextures);
     for (int i = 0; i < d->ntextures; i++) {
@@ -437,6 +454,7 @@ int lower_scene(const rt_scene_desc *d, LoweredScene *out) {
         s.has_moving |= d->boundary_prims[i].kind == RT_PRIM_MOVING_SPHERE;
     }
     const std::vector<rt_dmaterial> mats = to_dmaterials(d, s);
+    ball_fast_media(d, mats, s);
     const std::vector<rt_dtexture> texs = to_dtextures(d, s);
     const std::vector<rt_dinstance> insts = to_dinstances(d);
     const std::vector<rt_dmedium> media = to_dmedia(d);

@@ -23,6 +23,11 @@ struct SceneInfo {
     // medium cell: primitives [cell_first, cell_first + cell_n) are copies of those near the ball
     int cell_first = 0, cell_n = 0;
     float cell_c[3] = {0, 0, 0}, cell_r2 = 0, cell_rin2 = 0;
+    // the ball waves' fused in-ball step (rt_kernel.hip stage 3) may run: a medium cell, at most
+    // two media, each with an isotropic material whose texture the host resolved to a constant
+    // (material flag 2); ball_alb: those constants, in list order
+    bool ball_fast = false;
+    float ball_alb[2][3] = {{0, 0, 0}, {0, 0, 0}};
     int ngroups = 0;
     uint32_t root = 0;
     int has_bvh = 0, nmedia = 0, bvh_depth = 0, nnodes = 0, nprims = 0, bvh_width = 2, ninstances = 0;
@@ -46,6 +51,15 @@ int validate_desc(const rt_scene_desc *d);
 
 // `d` has passed validate_desc.  RT_OK, or the error of rt_last_error().
 int lower_scene(const rt_scene_desc *d, LoweredScene *out);
+
+}  // namespace rtnw
+
+// Diagnostics, exported from the library but not part of rt_hip.h (capi_scene.cpp; the prototype
+// tests/test_ball_fast.py binds): 1 when lower_scene enables the ball waves' fused in-ball step
+// for `d` (SceneInfo.ball_fast), 0 when not, or the error code (negative).  No HIP call.
+extern "C" int rt_scene_desc_ball_fast(const rt_scene_desc *d);
+
+namespace rtnw {
 
 inline double clock_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

@@ -168,6 +168,10 @@ enum {
 // ball-wave counters: ball-wave iterations, their live lanes and traversal rounds summed over
 // them, segments the medium cell decided (in ball waves), paths a normal wave could not push
 // (the ball's pool full), paths pushed into the ball's pool / the others' pool, paths taken
+// RT_FLAG_PROFILE reuses the RT_STAT_BALL slots with another meaning (rt_kernel.hip's epilogue,
+// capi_render.cpp read_counters): [0..3] the ball waves' claim / traverse / media / shade
+// cycles, [4] their iterations, [5] all waves' iterations, [6] the fused in-ball step's trips,
+// [7] those trips' cycles (part of [1]).
 enum { RT_BALL_ITERS = 0, RT_BALL_LIVE, RT_BALL_ROUNDS, RT_BALL_CELL_BALL, RT_BALL_DENIED, RT_BALL_PUSH_IN,
        RT_BALL_PUSH_OUT, RT_BALL_TAKEN, RT_BALL_N };
 // shading-stage sampler (rt_device.h coop_reject_mixed), wave-level: local candidate trips and
