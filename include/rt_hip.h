@@ -415,6 +415,50 @@ int rt_denoise_dev(int device, int nx, int ny, const float *color_dev, const flo
                    const float *moments_dev, const int32_t *spp_dev, const rt_denoise_params *dp,
                    float *out_dev, void *stream);
 
+/* ------------------------------- firefly clamp ahead of the denoiser */
+typedef struct rt_firefly_params {       /* 32 bytes */
+    int32_t demodulate;    /* 0 / 1 */
+    int32_t radius;        /* 1..3 */
+    int32_t min_similar;   /* 1..(2r+1)^2 - 1 */
+    float k;               /* >= 1 */
+    float floor;           /* >= 0, finite */
+    float cos_normal;      /* -1..1 */
+    float sigma_depth;     /* >= 0 */
+    float sigma_albedo;    /* >= 0 */
+} rt_firefly_params;
+/* Guide-aware outlier clamp of an nx x ny image, one Jacobi pass (every value read is an
+ * input).  With a' = max(albedo, 0.01) per channel when demodulate, else 1, a pixel's
+ * luminance is l = the sum of colour / a' over the channels.  A neighbour q within `radius`
+ * of p (a (2r+1)^2 window without its centre; neighbours outside the image do not exist) is
+ * similar when n_p . n_q >= cos_normal, |z_p - z_q| <= sigma_depth * min(z_p, z_q) + 1e-6 and
+ * |s_p - s_q| <= sigma_albedo * min(s_p, s_q) + 1e-6, s the sum of the raw albedo's channels.
+ * A pixel with at least min_similar similar neighbours whose l exceeds
+ * bound = k * (their mean l) + floor is scaled by ratio = bound / l: colour, and the moments
+ * as if every sample of the pixel had been scaled (m1 * ratio, m2 * ratio^2), so they feed
+ * rt_denoise as they are.  Every other pixel is copied bit for bit (ratio 1).  A one-pixel
+ * light keeps its value: its guide albedo is its emission, no neighbour resembles it, and it
+ * stays below min_similar.  Misses (normal 0, depth 0) resemble each other only when
+ * cos_normal <= 0.  The exact float32 statement is tests/test_firefly_spec.py.  Inputs must be
+ * finite and depths non-negative.  Suggested: demodulate 1, radius 2, min_similar 3, k 8,
+ * floor 0.01, cos_normal 0.9, sigma_depth 0.1, sigma_albedo 0.25 (what the
+ * clamp buys, and that it never lowers the error against a reference).
+ * Host buffers: color nx*ny*3; albedo, normal, depth as rt_render_features writes them;
+ * moments nx*ny*2 or NULL; out nx*ny*3, not color (neighbours are read: the pass cannot run
+ * in place); out_moments nx*ny*2 or NULL, needs moments and may be moments itself; ratio nx*ny
+ * or NULL; *ms (when non-NULL) receives the kernel's time in ms.  Synchronous.
+ * RT_ERR_INVALID for a null required pointer, nx or ny < 1 or nx * ny >= 2^31, a parameter
+ * outside the ranges above or NaN, out_moments without moments, and out == color (all checked
+ * before the device is touched, the parameter named in rt_last_error()). */
+int rt_firefly(int device, int nx, int ny, const float *color, const float *albedo, const float *normal,
+               const float *depth, const float *moments, const rt_firefly_params *fp,
+               float *out, float *out_moments, float *ratio, double *ms);
+/* The same on device buffers, enqueued on `stream`: color_dev 3 floats per pixel, guides_dev
+ * from rt_render_features_dev; moments_dev, out_moments_dev and ratio_dev may be NULL.  No
+ * workspace: calls may overlap. */
+int rt_firefly_dev(int device, int nx, int ny, const float *color_dev, const float *guides_dev,
+                   const float *moments_dev, const rt_firefly_params *fp, float *out_dev,
+                   float *out_moments_dev, float *ratio_dev, void *stream);
+
 /* Diagnostic: the device's float transcendentals of the path on n host inputs (out: n
  * floats) — fn 0 the megakernel's sinf (texture.h:36, 55), 2 its asinf and 4 its
  * atan2f(a, b) (hitable.h:15-16), all restated from glibc (rt_libm.h); 1, 3, 5 ocml's

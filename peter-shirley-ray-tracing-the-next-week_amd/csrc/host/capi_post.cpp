@@ -1,15 +1,18 @@
-// capi_post.cpp — what runs beside a render: the first-hit feature buffers (rt_features.hip)
-// and the à-trous denoiser (rt_denoise.hip).
+// capi_post.cpp — what runs beside a render: the first-hit feature buffers (rt_features.hip),
+// the à-trous denoiser (rt_denoise.hip) and the firefly clamp ahead of it (rt_firefly.hip).
+#include <cmath>
 #include <map>
 #include <mutex>
 
 #include "capi_internal.h"
 #include "../hip/rt_features.h"
 #include "../hip/rt_denoise.h"
+#include "../hip/rt_firefly.h"
 
-// the units' launchers, set by their static initialisers (rt_features.h, rt_denoise.h)
+// the units' launchers, set by their static initialisers (rt_features.h, rt_denoise.h, rt_firefly.h)
 RtFeaturesLaunch rt_features_launch = {nullptr, nullptr};
 RtDenoiseLaunch rt_denoise_launch = {nullptr, nullptr};
+RtFireflyLaunch rt_firefly_launch = {nullptr};
 
 // ------------------------------------------------ first-hit features (rt_hip.h)
 // The argument checks of both entry points, the scene's last: all before any HIP call.
@@ -121,6 +124,33 @@ static int denoise_run(int device, int nx, int ny, const float *color, const flo
     return RT_OK;
 }
 
+// ------------------------------------------------ firefly clamp (rt_hip.h)
+// `nulls`: a required pointer is missing; `same`: out is color.  All before any HIP call.
+static int firefly_check(const char *fn, int nx, int ny, bool nulls, const rt_firefly_params *fp, bool moments,
+                         bool out_moments, bool same) {
+    const std::string f(fn);
+    if (nulls || !fp) return fail(RT_ERR_INVALID, f + ": null argument");
+    if (nx < 1 || ny < 1 || (uint64_t)nx * (uint64_t)ny > 0x7FFFFFFFull)
+        return fail(RT_ERR_INVALID, f + ": nx and ny must be at least 1 (and nx * ny below 2^31)");
+    if (fp->demodulate != 0 && fp->demodulate != 1) return fail(RT_ERR_INVALID, f + ": demodulate must be 0 or 1");
+    if (fp->radius < 1 || fp->radius > 3) return fail(RT_ERR_INVALID, f + ": radius must be in 1..3");
+    const int window = (2 * fp->radius + 1) * (2 * fp->radius + 1) - 1;
+    if (fp->min_similar < 1 || fp->min_similar > window)
+        return fail(RT_ERR_INVALID, f + ": min_similar must be in 1..(2 radius + 1)^2 - 1");
+    if (!(fp->k >= 1.0f)) return fail(RT_ERR_INVALID, f + ": k must be at least 1 (and not NaN)");
+    if (!(fp->floor >= 0.0f) || !std::isfinite(fp->floor))
+        return fail(RT_ERR_INVALID, f + ": floor must be finite and not negative");
+    if (!(fp->cos_normal >= -1.0f && fp->cos_normal <= 1.0f))
+        return fail(RT_ERR_INVALID, f + ": cos_normal must be in -1..1");
+    if (!(fp->sigma_depth >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_depth must not be negative or NaN");
+    if (!(fp->sigma_albedo >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_albedo must not be negative or NaN");
+    if (out_moments && !moments) return fail(RT_ERR_INVALID, f + ": out_moments needs moments");
+    if (same) return fail(RT_ERR_INVALID, f + ": out must not be color (neighbours are read: not in place)");
+    if (!rt_firefly_launch.clamp)
+        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the firefly unit (rt_firefly.o)");
+    return RT_OK;
+}
+
 extern "C" {
 
 int rt_render_features_dev(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
@@ -193,6 +223,57 @@ int rt_denoise(int device, int nx, int ny, const float *color, const float *albe
         return rc;
     HIP_TRY(hipEventRecord(ev[1], nullptr));
     HIP_TRY(hipMemcpy(out, d + off_o, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (ms) {
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        *ms = (double)t;
+    }
+    return RT_OK;
+}
+
+int rt_firefly_dev(int device, int nx, int ny, const float *color_dev, const float *guides_dev, const float *moments_dev,
+                   const rt_firefly_params *fp, float *out_dev, float *out_moments_dev, float *ratio_dev, void *stream) {
+    if (int rc = firefly_check("rt_firefly_dev", nx, ny, !color_dev || !guides_dev || !out_dev, fp, moments_dev != nullptr,
+                               out_moments_dev != nullptr, out_dev == color_dev))
+        return rc;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(rt_firefly_launch.clamp(nx, ny, color_dev, guides_dev, moments_dev, fp, out_dev, out_moments_dev, ratio_dev,
+                                    (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_firefly(int device, int nx, int ny, const float *color, const float *albedo, const float *normal, const float *depth,
+               const float *moments, const rt_firefly_params *fp, float *out, float *out_moments, float *ratio, double *ms) {
+    if (int rc = firefly_check("rt_firefly", nx, ny, !color || !albedo || !normal || !depth || !out, fp, moments != nullptr,
+                               out_moments != nullptr, out == color))
+        return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t npix = (size_t)nx * ny;
+    std::vector<float> g(npix * RT_GUIDE_FLOATS);
+    for (size_t q = 0; q < npix; q++) {   // the packed guides; coverage is not read by the clamp
+        float *v = g.data() + q * RT_GUIDE_FLOATS;
+        v[0] = albedo[3 * q]; v[1] = albedo[3 * q + 1]; v[2] = albedo[3 * q + 2]; v[3] = 0.f;
+        v[4] = normal[3 * q]; v[5] = normal[3 * q + 1]; v[6] = normal[3 * q + 2]; v[7] = depth[q];
+    }
+    // one allocation: guides, colour, moments, out, out moments, ratio (the guides first: 16-B loads)
+    const size_t off_c = npix * RT_GUIDE_FLOATS, off_m = off_c + npix * 3, off_o = off_m + npix * 2, off_om = off_o + npix * 3,
+                 off_r = off_om + npix * 2, total = off_r + npix;
+    DevBuf staging;
+    Events<2> ev;
+    if (int rc = staging.reserve(total * sizeof(float))) return rc;
+    float *d = (float *)staging.p;
+    HIP_TRY(hipMemcpy(d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d + off_c, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
+    if (moments) HIP_TRY(hipMemcpy(d + off_m, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipEventCreate(&ev[0]));
+    HIP_TRY(hipEventCreate(&ev[1]));
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
+    HIP_TRY(rt_firefly_launch.clamp(nx, ny, d + off_c, d, moments ? d + off_m : nullptr, fp, d + off_o,
+                                    out_moments ? d + off_om : nullptr, ratio ? d + off_r : nullptr, nullptr));
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipMemcpy(out, d + off_o, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_moments) HIP_TRY(hipMemcpy(out_moments, d + off_om, npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (ratio) HIP_TRY(hipMemcpy(ratio, d + off_r, npix * sizeof(float), hipMemcpyDeviceToHost));
     if (ms) {
         float t = 0.f;
         HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));

@@ -131,6 +131,17 @@ class RtDenoiseParams(ctypes.Structure):
 DENOISE_DEFAULTS = dict(iterations=3, demodulate=1, sigma_color=2.0, sigma_depth=1.0)
 
 
+class RtFireflyParams(ctypes.Structure):
+    _fields_ = [("demodulate", ctypes.c_int32), ("radius", ctypes.c_int32), ("min_similar", ctypes.c_int32),
+                ("k", ctypes.c_float), ("floor", ctypes.c_float), ("cos_normal", ctypes.c_float),
+                ("sigma_depth", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
+
+
+# the firefly clamp's suggested settings (DESIGN.md §7e records the sweep that chose them)
+FIREFLY_DEFAULTS = dict(demodulate=1, radius=2, min_similar=3, k=8.0, floor=0.01, cos_normal=0.9, sigma_depth=0.1,
+                        sigma_albedo=0.25)
+
+
 class RtCheckpoint(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("nx", ctypes.c_int32),
                 ("ny", ctypes.c_int32), ("samples_done", ctypes.c_uint32), ("max_depth", ctypes.c_int32),
@@ -187,6 +198,12 @@ def lib():
             "rt_denoise_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, P(RtDenoiseParams), ctypes.c_void_p,
                                               ctypes.c_void_p]),
+            "rt_firefly": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(RtFireflyParams),
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_double)]),
+            "rt_firefly_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, P(RtFireflyParams), ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
             "rt_device_alloc": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, P(ctypes.c_void_p)]),
             "rt_device_free": (ctypes.c_int, [ctypes.c_void_p]),
             "rt_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
@@ -219,10 +236,11 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass and the denoiser
+        # the feature pass, the denoiser and the firefly clamp
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
                     "rt_copy_to_device",
-                    "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev"}
+                    "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
+                    "rt_firefly", "rt_firefly_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -547,6 +565,47 @@ def denoise(color, features, moments=None, spp=None, *, iterations=None, demodul
                             None if m is None else m.ctypes.data, None if smap is None else smap.ctypes.data,
                             ctypes.byref(dp), out.ctypes.data, ctypes.byref(ms)))
     return (out, ms.value) if timing else out
+
+
+# -------------------------------------------------------------- firefly clamp
+def firefly_params(demodulate=None, radius=None, min_similar=None, k=None, floor=None, cos_normal=None,
+                   sigma_depth=None, sigma_albedo=None):
+    given = dict(demodulate=demodulate, radius=radius, min_similar=min_similar, k=k, floor=floor,
+                 cos_normal=cos_normal, sigma_depth=sigma_depth, sigma_albedo=sigma_albedo)
+    v = {n: FIREFLY_DEFAULTS[n] if x is None else x for n, x in given.items()}
+    return RtFireflyParams(demodulate=int(v["demodulate"]), radius=int(v["radius"]), min_similar=int(v["min_similar"]),
+                           k=v["k"], floor=v["floor"], cos_normal=v["cos_normal"], sigma_depth=v["sigma_depth"],
+                           sigma_albedo=v["sigma_albedo"])
+
+
+def firefly(color, features, moments=None, *, demodulate=None, radius=None, min_similar=None, k=None, floor=None,
+            cos_normal=None, sigma_depth=None, sigma_albedo=None, device: int = 0, timing: bool = False,
+            want_ratio: bool = False):
+    """Guide-aware firefly clamp (rt_firefly) of `color` [ny, nx, 3], to run ahead of `denoise`:
+    a pixel whose demodulated luminance exceeds k times the mean of its similar neighbours
+    (normal, depth and albedo of `features`, Scene.render_features' dict, within `radius`)
+    plus `floor` is scaled down to that bound, when it has at least `min_similar` of them.
+    `moments` [ny, nx, 2] are scaled along, so they feed `denoise` unchanged.  Unset settings
+    take FIREFLY_DEFAULTS.  Returns the clamped image, then the moments when `moments` was
+    given, the per-pixel scale [ny, nx] with want_ratio=True and the kernel's ms with
+    timing=True (a tuple when more than the image)."""
+    c = np.ascontiguousarray(color, np.float32)
+    ny, nx, _ = c.shape
+    a = np.ascontiguousarray(features["albedo"], np.float32).reshape(ny, nx, 3)
+    n = np.ascontiguousarray(features["normal"], np.float32).reshape(ny, nx, 3)
+    z = np.ascontiguousarray(features["depth"], np.float32).reshape(ny, nx)
+    m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
+    fp = firefly_params(demodulate, radius, min_similar, k, floor, cos_normal, sigma_depth, sigma_albedo)
+    out = np.zeros_like(c)
+    om = None if m is None else np.zeros_like(m)
+    ratio = np.zeros((ny, nx), np.float32) if want_ratio else None
+    ms = ctypes.c_double(0.0)
+    _check(lib().rt_firefly(device, nx, ny, c.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,
+                            None if m is None else m.ctypes.data, ctypes.byref(fp), out.ctypes.data,
+                            None if om is None else om.ctypes.data, None if ratio is None else ratio.ctypes.data,
+                            ctypes.byref(ms)))
+    res = [out] + ([om] if om is not None else []) + ([ratio] if want_ratio else []) + ([ms.value] if timing else [])
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 # ------------------------------------------------------------ multi-GPU (RCCL)

@@ -19,6 +19,13 @@ step_spp 64, floor 0.01, tolerance 0.05; its moments and count map), and reports
 --timing adds the denoiser's kernel ms for 1..5 iterations (the first figure holds the prepare
 kernel) and the feature pass's wall ms on 500x500 and 1000x1000.
 
+--firefly adds every row once more with the firefly clamp (rt_firefly, rtnw.FIREFLY_DEFAULTS)
+ahead of the filter: the clamped pixels, the clamp's kernel ms and the gamma RMS of the clamped
+image before and after the filter.  With --sweep it runs, in place of the
+filter's grid, the grid over k and radius that chose those defaults, with --timing the clamp's
+kernel ms by radius beside the à-trous iterations'.  --cap overrides the configurations' sample
+caps (a low-count regime).
+
 Writes <out>/denoise_probe.json and <out>/denoise_probe.md.  Not run by any test.
 """
 import argparse
@@ -75,6 +82,8 @@ def main():
     ap.add_argument("--feature-spp", type=int, default=16)
     ap.add_argument("--variance-filter", type=int, default=0, choices=(0, 1), help="1: rows with the pre-filter too")
     ap.add_argument("--guard-radius", type=int, default=None, help="the adaptive input's guard radius (0..8)")
+    ap.add_argument("--firefly", action="store_true", help="rows with the firefly clamp ahead of the filter too")
+    ap.add_argument("--cap", type=int, default=None, help="overrides the configurations' sample caps")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--scale", type=float, default=1.0, help="scales the image side and the cap (rehearsals)")
@@ -87,6 +96,8 @@ def main():
     for cfg in args.configs.split(","):
         scene_name, nx, ny, cap = CONFIGS[cfg]
         nx, ny, cap = max(8, int(nx * args.scale)), max(8, int(ny * args.scale)), max(args.min_spp, int(cap * args.scale))
+        if args.cap:
+            cap = max(args.min_spp, args.cap)
         cam_name, bg, depth = rtnw.SCENE_DEFAULTS[scene_name]
         scene = rtnw.Scene.builtin(scene_name)
         cam = rtnw.Camera.preset(cam_name, nx, ny)
@@ -133,7 +144,7 @@ def main():
                    "render_ms": statistics.median(t[name]), "features_ms": feat_ms,
                    "denoise_ms": statistics.median(t["denoise_" + name]), "denoise_kernel_ms": statistics.median(kms[name]),
                    "rms_raw": gamma_rms(color, ref), "rms_denoised": gamma_rms(out, ref), "variance_filter": 0,
-                   "guard_radius": args.guard_radius if name == "adaptive" else None}
+                   "guard_radius": args.guard_radius if name == "adaptive" else None, "firefly": 0}
             row["total_raw_ms"] = row["render_ms"]
             row["total_denoised_ms"] = row["render_ms"] + row["features_ms"] + row["denoise_ms"]
             rows.append(row)
@@ -147,7 +158,46 @@ def main():
                 row["total_denoised_ms"] = row["render_ms"] + row["features_ms"] + row["denoise_ms"]
                 rows.append(row)
                 print(json.dumps(row), flush=True)
-        if args.sweep:
+        if args.firefly:                        # the same inputs through the clamp, then the filter
+            for name in renders:
+                color, mom, spp, samples, _ = last[name]
+                runs = [rtnw.firefly(color, f, mom, want_ratio=True, timing=True) for _ in range(args.rounds + 2)][2:]
+                cl, cmom, ratio, _ = runs[-1]
+                base = next(r for r in rows if r["config"] == cfg and r["input"] == name and r["variance_filter"] == 0
+                            and not r["firefly"])
+                for vf in ((0, 1) if args.variance_filter else (0,)):
+                    dn = [timed(lambda: rtnw.denoise(cl, f, cmom, spp, variance_filter=vf, timing=True))
+                          for _ in range(args.rounds + 1)][1:]
+                    row = dict(base, variance_filter=vf, firefly=1, **{"firefly_" + k: v for k, v in rtnw.FIREFLY_DEFAULTS.items()},
+                               firefly_kernel_ms=statistics.median(r[3] for r in runs), clamped_pixels=int((ratio != 1).sum()),
+                               rms_clamped=gamma_rms(cl, ref), denoise_ms=statistics.median(ms for ms, _ in dn),
+                               denoise_kernel_ms=statistics.median(k for _, (_, k) in dn),
+                               rms_denoised=gamma_rms(dn[-1][1][0], ref))
+                    row["total_denoised_ms"] = row["render_ms"] + row["features_ms"] + row["denoise_ms"]
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+        if args.firefly and args.sweep:         # the grid that chose rtnw.FIREFLY_DEFAULTS
+            for k in (2.0, 4.0, 8.0, 16.0):
+                for radius in (1, 2):
+                    r = {"config": cfg, "firefly_k": k, "firefly_radius": radius}
+                    for name in renders:
+                        color, mom, spp, _, _ = last[name]
+                        cl, cmom, ratio = rtnw.firefly(color, f, mom, k=k, radius=radius, want_ratio=True)
+                        r["clamped_" + name] = int((ratio != 1).sum())
+                        r["rms_clamped_" + name] = gamma_rms(cl, ref)
+                        for vf in (0, 1):
+                            r[f"rms_vf{vf}_" + name] = gamma_rms(rtnw.denoise(cl, f, cmom, spp, variance_filter=vf), ref)
+                    sweep.append(r)
+                    print(json.dumps(r), flush=True)
+            r = {"config": cfg, "firefly_k": None, "firefly_radius": None}   # the clamp off, for comparison
+            for name in renders:
+                color, mom, spp, _, _ = last[name]
+                r["rms_clamped_" + name] = gamma_rms(color, ref)
+                for vf in (0, 1):
+                    r[f"rms_vf{vf}_" + name] = gamma_rms(rtnw.denoise(color, f, mom, spp, variance_filter=vf), ref)
+            sweep.append(r)
+            print(json.dumps(r), flush=True)
+        elif args.sweep:
             for it in (3, 4, 5, 6):
                 for sc in (1.0, 2.0, 4.0, 8.0, 16.0):
                     for sd in (0.25, 1.0, 4.0):
@@ -180,6 +230,10 @@ def main():
                 for it in range(1, 6):
                     ks = [rtnw.denoise(c2, f2, m2, spp, iterations=it, timing=True)[1] for _ in range(7)]
                     r[f"kernel_ms_{it}_iterations"] = statistics.median(ks[2:])
+                if args.firefly:                # the clamp's kernel by radius, on the same data
+                    for radius in (1, 2, 3):
+                        ks = [rtnw.firefly(c2, f2, m2, radius=radius, timing=True)[-1] for _ in range(9)]
+                        r[f"firefly_kernel_ms_radius_{radius}"] = statistics.median(ks[2:])
                 timing.append(r)
                 print(json.dumps(r), flush=True)
             for rep in (1, 2):
@@ -196,11 +250,13 @@ def main():
         json.dump({"tool": "tools/denoise_probe.py", "args": vars(args), "rows": rows, "sweep": sweep, "timing": timing},
                   f, indent=1)
     with open(os.path.join(args.out, "denoise_probe.md"), "w") as f:
-        f.write("| config | input | variance filter | samples (share of cap) | render ms | features ms | denoise ms (kernels) | total raw ms | "
-                "total denoised ms | gamma RMS raw | gamma RMS denoised |\n|---|---|---|---|---|---|---|---|---|---|---|\n")
+        f.write("| config | input | firefly clamp (pixels clamped, kernel ms, gamma RMS clamped) | variance filter | samples (share of cap) | render ms | features ms | denoise ms (kernels) | total raw ms | "
+                "total denoised ms | gamma RMS raw | gamma RMS denoised |\n|---|---|---|---|---|---|---|---|---|---|---|---|\n")
         for r in rows:
             f.write(f"| {r['config']} {r['scene']} {r['nx']}x{r['ny']} cap {r['cap']} | {r['input']}"
-                    f"{'' if r['guard_radius'] is None else ' guard ' + str(r['guard_radius'])} | {r['variance_filter']} | "
+                    f"{'' if r['guard_radius'] is None else ' guard ' + str(r['guard_radius'])} | "
+                    + (f"on ({r['clamped_pixels']}, {r['firefly_kernel_ms']:.4f}, {r['rms_clamped']:.5f})" if r["firefly"] else "off")
+                    + f" | {r['variance_filter']} | "
                     f"{r['samples']:.0f} ({r['samples_share']:.3f}) | {r['render_ms']:.2f} | {r['features_ms']:.2f} | "
                     f"{r['denoise_ms']:.2f} ({r['denoise_kernel_ms']:.3f}) | {r['total_raw_ms']:.2f} | "
                     f"{r['total_denoised_ms']:.2f} | {r['rms_raw']:.5f} | {r['rms_denoised']:.5f} |\n")
