@@ -243,6 +243,11 @@ typedef struct rt_stats {
     double lane_scatters;         /*   lanes that scattered (SIMD efficiency = this / 64x wave_shade_passes) */
     double cycles_scatter;        /* RT_FLAG_PROFILE: wave cycles in the material scatter branches (part of
                                          cycles_shade) */
+    double ball_fused_scatters;   /* RT_FLAG_COUNT: lanes served by the ball waves' fused in-ball step, that is
+                                         segments that scattered at a medium there (part of lane_scatters) */
+    double ball_fused_declined;   /*   eligible lanes a trip of that step left to the generic stages (a cell
+                                         primitive first, the cell undecided, or no scatter); both are 0 in a
+                                         kernel variant without ball waves */
 } rt_stats;
 
 typedef struct rt_scene rt_scene; /* opaque; owns device copies */

@@ -508,7 +508,7 @@ struct Counters {
     // material divergence of the shading stage: wave passes through the scatter
     // branches, the distinct materials each pass ran, and the lanes that scattered
     uint64_t w_shade = 0, w_kinds = 0, l_scatter = 0;
-    uint64_t ball[RT_BALL_N] = {0, 0, 0, 0, 0, 0, 0, 0};   // the ball waves (rt_layout.h RT_BALL_*), wave-level
+    uint64_t ball[RT_BALL_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // the ball waves (rt_layout.h RT_BALL_*), wave-level
     uint64_t w_local = 0;                                  // coop_reject_mixed's local candidate trips (part of w_rius)
     uint64_t sampler[RT_SAMPLER_N] = {0, 0, 0, 0};         // rt_layout.h RT_SAMPLER_*, wave-level (lane 0)
     __device__ __forceinline__ void prim(int kind) {

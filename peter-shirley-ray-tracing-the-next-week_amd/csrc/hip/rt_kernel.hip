@@ -735,8 +735,12 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                                 cnt.media = c_med;
                             }
                             if (commit) { cnt.shades++; cnt.l_scatter++; }
-                            const uint64_t nc = wballot(commit);
-                            if (lane == 0) cnt.ball[RT_BALL_CELL_BALL] += (uint64_t)__popcll(nc);
+                            const uint64_t nc = wballot(commit), nd = wballot(el && !commit);
+                            if (lane == 0) {
+                                cnt.ball[RT_BALL_CELL_BALL] += (uint64_t)__popcll(nc);
+                                cnt.ball[RT_BALL_FUSED] += (uint64_t)__popcll(nc);       // lanes this trip served
+                                cnt.ball[RT_BALL_DECLINED] += (uint64_t)__popcll(nd);    // ... and left to the generic stages
+                            }
                         }
                         // material.h:145-149 with the lane's own rejection loop (all 64 lanes run the rounds)
                         const uint64_t trips0 = cnt.w_rius, local0 = cnt.w_local;   // (kCount)

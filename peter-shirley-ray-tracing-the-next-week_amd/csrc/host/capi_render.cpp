@@ -163,16 +163,20 @@ int read_counters(rt_scene *s, bool count, bool prof, double items, rt_stats *st
         stats->wave_shade_passes = (double)sh[0];
         stats->wave_shade_kinds = (double)sh[1];
         stats->lane_scatters = (double)sh[2];
-        if (std::getenv("RTNW_TRACE")) {   // the ball waves (rt_kernel.hip stage 6), diagnostics only
-            unsigned long long b[RT_BALL_N];
-            HIP_TRY(hipMemcpy(b, (unsigned long long *)s->stats + RT_STAT_BALL, sizeof b, hipMemcpyDeviceToHost));
+        // the ball waves (rt_kernel.hip stage 6): a variant without them leaves the slots 0
+        unsigned long long b[RT_BALL_N];
+        HIP_TRY(hipMemcpy(b, (unsigned long long *)s->stats + RT_STAT_BALL, sizeof b, hipMemcpyDeviceToHost));
+        stats->ball_fused_scatters = (double)b[RT_BALL_FUSED];
+        stats->ball_fused_declined = (double)b[RT_BALL_DECLINED];
+        if (std::getenv("RTNW_TRACE")) {   // diagnostics only
             std::fprintf(stderr,
                          "rtnw ball waves: iterations %llu, live lanes / iteration %.1f, traversal rounds / iteration %.2f, "
                          "cell-decided segments in ball waves %llu, pushes refused (pool full) %llu (of %.0f segments), pushed in %llu, "
-                         "pushed out %llu, taken %llu\n",
+                         "pushed out %llu, taken %llu; fused in-ball step: lanes served %llu, declined %llu\n",
                          b[RT_BALL_ITERS], b[RT_BALL_ITERS] ? (double)b[RT_BALL_LIVE] / b[RT_BALL_ITERS] : 0.0,
                          b[RT_BALL_ITERS] ? (double)b[RT_BALL_ROUNDS] / b[RT_BALL_ITERS] : 0.0, b[RT_BALL_CELL_BALL],
-                         b[RT_BALL_DENIED], stats->segments, b[RT_BALL_PUSH_IN], b[RT_BALL_PUSH_OUT], b[RT_BALL_TAKEN]);
+                         b[RT_BALL_DENIED], stats->segments, b[RT_BALL_PUSH_IN], b[RT_BALL_PUSH_OUT], b[RT_BALL_TAKEN],
+                         b[RT_BALL_FUSED], b[RT_BALL_DECLINED]);
             unsigned long long r[RT_SAMPLER_N];
             HIP_TRY(hipMemcpy(r, (unsigned long long *)s->stats + RT_STAT_SAMPLER, sizeof r, hipMemcpyDeviceToHost));
             std::fprintf(stderr,

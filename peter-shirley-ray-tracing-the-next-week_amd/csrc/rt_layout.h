@@ -162,18 +162,21 @@ enum {
 enum {
     RT_STAT_PROF = RT_CNT_N, RT_STAT_WAVE = RT_CNT_N + 4, RT_STAT_TIME = RT_CNT_N + 9, RT_STAT_SHADE = RT_CNT_N + 16,
     RT_STAT_BALL = RT_CNT_N + 20,   // RT_FLAG_COUNT, the ball waves (rt_kernel.hip stage 6): RT_BALL_*
-    RT_STAT_SAMPLER = RT_CNT_N + 28,   // RT_FLAG_COUNT, the shading stage's rejection sampler: RT_SAMPLER_*
-    RT_STATS_LEN = RT_CNT_N + 32
+    RT_STAT_SAMPLER = RT_CNT_N + 30,   // RT_FLAG_COUNT, the shading stage's rejection sampler: RT_SAMPLER_*
+    RT_STATS_LEN = RT_CNT_N + 34
 };
 // ball-wave counters: ball-wave iterations, their live lanes and traversal rounds summed over
 // them, segments the medium cell decided (in ball waves), paths a normal wave could not push
-// (the ball's pool full), paths pushed into the ball's pool / the others' pool, paths taken
+// (the ball's pool full), paths pushed into the ball's pool / the others' pool, paths taken;
+// the fused in-ball step (rt_kernel.hip stage 3), lane-level: the lanes its trips served (the
+// segments that scattered there) and the eligible lanes its trips declined (rt_stats
+// ball_fused_scatters, ball_fused_declined)
 // RT_FLAG_PROFILE reuses the RT_STAT_BALL slots with another meaning (rt_kernel.hip's epilogue,
 // capi_render.cpp read_counters): [0..3] the ball waves' claim / traverse / media / shade
 // cycles, [4] their iterations, [5] all waves' iterations, [6] the fused in-ball step's trips,
 // [7] those trips' cycles (part of [1]).
 enum { RT_BALL_ITERS = 0, RT_BALL_LIVE, RT_BALL_ROUNDS, RT_BALL_CELL_BALL, RT_BALL_DENIED, RT_BALL_PUSH_IN,
-       RT_BALL_PUSH_OUT, RT_BALL_TAKEN, RT_BALL_N };
+       RT_BALL_PUSH_OUT, RT_BALL_TAKEN, RT_BALL_FUSED, RT_BALL_DECLINED, RT_BALL_N };
 // shading-stage sampler (rt_device.h coop_reject_mixed), wave-level: local candidate trips and
 // cooperative rounds of all waves, and of the ball waves alone
 enum { RT_SAMPLER_LOCAL = 0, RT_SAMPLER_ROUNDS, RT_SAMPLER_BALL_LOCAL, RT_SAMPLER_BALL_ROUNDS, RT_SAMPLER_N };

@@ -5,7 +5,8 @@ A literal table of cases (CASES) maps, through np.random.default_rng(seed), to s
 descriptors (rtnw.SceneDesc.from_arrays) that reach the structural paths rt_scene_create
 chooses among and the twelve built-in scenes do not: both sides of the flat-scan, pre-scan,
 LDS-media, medium-cell and LDS-BVH limits, every boundary kind of a medium, instance chains of
-every op order, and textures and materials on every primitive kind.  The oracle
+every op order, textures and materials on every primitive kind, and the ball waves' fused
+in-ball step (ball_*, also under tests/test_gpu_ball_generated.py).  The oracle
 (oracle.render_desc) says what the image of each is.
 
 Every case names its TARGET: the primitives, media or textures it exists for.
@@ -362,6 +363,93 @@ def cell(b, variant):
               b.sphere((c[0] + 0.3, c[1] + 1.6, c[2]), 0.15, red), target=True)
 
 
+BALL_R = 1.0
+BALL_ALB = ((0.85, 0.55, 0.25), (0.3, 0.6, 0.9), (0.5, 0.8, 0.4))   # the ball's, the second medium's, the third's
+# the ball's density by variant (mean free path 1 / density; dense, "deep", where that is below R / 2)
+BALL_DENSITY = {"one_medium": 8.0, "dense_first": 6.0, "dense_second": 6.0, "in_fog_on_ground": 3.0, "full_cell": 4.0,
+                "thin": 0.5, "negative_radius": 8.0, "solid": 1e30, "three_media": 6.0, "noise_medium": 6.0,
+                "with_instance": 6.0, "camera_inside": 4.0}
+BALL_QUALIFY = ("one_medium", "dense_first", "dense_second", "in_fog_on_ground", "full_cell", "thin", "negative_radius",
+                "solid", "camera_inside")                        # rt_scene_desc_ball_fast = 1, and the step can run
+BALL_DECLINE = ("three_media", "noise_medium", "with_instance")  # lowering says 0, 0, 1; the step never runs
+BALL_LOOKFROM = (0.0, 1.7, 2.7)
+# camera_inside: full_cell seen from inside the ball, so that camera rays, which carry a time of their own, start
+# there (behind the glass shell every segment inside the ball has time 0 already: a dielectric leaves it so)
+BALL_INSIDE_LOOKFROM = (0.25, 1.45, 0.6)
+
+
+def ball_centre(variant):
+    """in_fog_on_ground's ball floats 0.01 above the ground, less than its margin R / 64 + 1e-3 |c|max = 0.0166."""
+    return (0.0, BALL_R + 0.01, 0.0) if variant == "in_fog_on_ground" else (0.0, 1.3, 0.0)
+
+
+def ball(b, variant):
+    """The ball waves' fused in-ball step (rt_kernel.hip stage 3) on a BVH scene of more than 64
+    primitives without an instance chain: one dense sphere-bounded ball of radius BALL_R that
+    fills most of the frame, every medium an isotropic of a constant texture (BALL_ALB: distinct,
+    no component 0 or 1), the ground and 77 small spheres out of the ball's reach."""
+    c, R, dens = ball_centre(variant), BALL_R, BALL_DENSITY[variant]
+    g = b.glass()
+    second = np.add(c, (0.6, 0.0, 0.0))   # the second medium's sphere (radius R): the lens is 56 % of the ball
+    avoid = [(c, R + 0.45), (second, R + 0.45), (BALL_LOOKFROM, 0.6)]
+    third_c, box_at = (3.0, 0.7, -1.5), (3.0, 0.0, -2.0)
+    if variant == "three_media":
+        avoid.append((third_c, 0.5 + 0.3))
+    if variant == "with_instance":
+        avoid.append((np.add(box_at, (0.3, 0.3, 0.3)), 1.0))
+    # The ball waves exist only in the kernel variant of the feature set "media" alone (rt_kernel.hip kBall):
+    # no checker texture, no pre-scanned primitive, no instance chain.  So the ground is a plain 4.8 x 4.8
+    # lambertian (box area 46) and the scene box is pinned to 12 x 5.8 x 12 by two spheres in its corners
+    # (area 566): neither the ground nor the ball's shell (24) reaches the pre-scan's 10 % of it.
+    # The ground is not a near primitive, except in in_fog_on_ground
+    b.add(ground(b, half=2.4, mat=b.lambert(b.const(0.5, 0.5, 0.45))))
+    b.add(b.sphere((-5.9, 0.3, -5.9), 0.1, b.lambert()), b.sphere((5.9, 5.9, 5.9), 0.1, b.lambert()))
+    if variant == "in_fog_on_ground":
+        # spheres of radius 0.2 whose boxes stay just outside the ball's reach R + 0.0166 (the rule measures
+        # boxes: a corner is up to 0.2 sqrt(3) nearer than the centre): a ring resting on the ground at 1.15
+        # from the axis and one at the ball's height at 1.34.  A ray that leaves the ball downwards meets one
+        # of them, or a fog scatter, before the ground
+        ring = [b.sphere((1.15 * math.cos(a), 0.22, 1.15 * math.sin(a)), 0.2, b.rand_mat())
+                for a in np.arange(16) * (2 * math.pi / 16)]
+        ring += [b.sphere((1.34 * math.cos(a), c[1], 1.34 * math.sin(a)), 0.2, b.rand_mat())
+                 for a in (np.arange(16) + 0.5) * (2 * math.pi / 16) if math.sin(a) < 0.7]   # (not in the camera's way)
+        b.add(*ring, target=True)
+        avoid[0] = (c, R + 0.75)
+    b.add(*small_spheres(b, 75, lo=(-5, 0.15, -5), hi=(5, 4.0, 5), avoid=avoid))
+    rb = -R if variant == "negative_radius" else R
+
+    def the_ball():
+        if variant != "in_fog_on_ground":
+            b.add(b.sphere(c, rb, g), target=True)   # the glass shell: near primitive 1
+        b.medium(b.sphere(c, rb, g), dens, b.const(*BALL_ALB[0]), target=True)
+
+    def the_second():
+        tex = b.noise(4.0) if variant == "noise_medium" else b.const(*BALL_ALB[1])
+        # mean free path 1 / 1.5 = 0.67 R against the ball's 1 / 6: in the lens it scatters a fifth of the segments
+        b.medium(b.sphere(second, R, g), 1.5, tex, target=True)
+
+    if variant in ("dense_first", "three_media", "noise_medium", "with_instance"):
+        the_ball()      # the cell goes to medium 0: the ball, the first candidate of the greatest density
+        the_second()
+    elif variant == "dense_second":
+        the_second()    # medium 0 is a candidate too (the shell is its one near primitive), and
+        the_ball()      # the cell goes to medium 1: the ball, of strictly greater density
+    else:
+        the_ball()
+    if variant == "in_fog_on_ground":   # a scene-wide fog of mean free path 12.5, the ground's side 12; no cell candidate
+        b.medium(b.sphere((0.0, 0.0, 0.0), 30.0, g), 0.08, b.const(*BALL_ALB[1]), target=True)
+    if variant == "three_media":
+        b.medium(b.sphere(third_c, 0.5, g), 2.0, b.const(*BALL_ALB[2]))
+    if variant == "with_instance":   # far from the ball: the kernel variant with instance chains has no ball waves
+        b.add(*b.box((0, 0, 0), (0.6, 0.6, 0.6), b.lambert(), b.chain([("t", *box_at), ("r", 30.0)])))
+    if variant in ("full_cell", "camera_inside"):   # the shell + 3 inside the ball = RT_CELL_MAX near primitives
+        b.add(b.sphere((c[0] + 0.4, c[1], c[2]), 0.2, b.metal((0.9, 0.8, 0.7), 0.0)),
+              b.msphere((c[0] - 0.4, c[1] - 0.15, c[2] + 0.1), (c[0] - 0.4, c[1] + 0.2, c[2] + 0.1), 0, 1, 0.15,
+                        b.lambert(b.const(0.9, 0.1, 0.1))),     # centres 0.35 apart, radius 0.15
+              b.rect(XZ, c[0] - 0.4, c[0] + 0.4, c[2] - 0.4, c[2] + 0.4, c[1] - 0.5, b.lambert(b.const(0.2, 0.8, 0.3))),
+              target=True)
+
+
 def _op(b, kind):
     if kind == "t":
         return ("t", *b.rng.uniform(-0.35, 0.35, 3))
@@ -556,6 +644,13 @@ CASES = [
     *[_c(f"cell_{v}", (lambda v: lambda b: cell(b, v))(v), 500 + i, expect=dict(scan_groups=0),
          knobs=BVH + ("RTNW_PRESCAN", "RTNW_CELL"), lookfrom=(0.0, 2.0, 6.5), lookat=(0.0, 1.0, 0.0))
       for i, v in enumerate(("two_dense", "two_equal", "near4", "near5", "near_inst_moving", "dup_outside", "not_dense"))],
+    # 5b. the ball waves' fused in-ball step: the variants that run it, then those that must not
+    *[_c(f"ball_{v}", (lambda v: lambda b: ball(b, v))(v), 900 + i, nx=48, ny=32, spp=8,
+         max_depth=8 if v == "solid" else 50, expect=dict(scan_groups=0, lds_level=1, prescan=0),
+         knobs=BVH + ("RTNW_PRESCAN", "RTNW_CELL"), lookfrom=BALL_LOOKFROM, lookat=ball_centre(v))
+      for i, v in enumerate(BALL_QUALIFY[:8] + BALL_DECLINE)],
+    _c("ball_camera_inside", lambda b: ball(b, "camera_inside"), 911, nx=48, ny=32, spp=8, expect=dict(scan_groups=0, lds_level=1, prescan=0),
+       knobs=BVH + ("RTNW_PRESCAN", "RTNW_CELL"), lookfrom=BALL_INSIDE_LOOKFROM, lookat=(-0.4, 1.32, 0.1), vfov=70.0),
     # 6. LDS-resident BVH limits: nnodes <= 1024, nprims < 4096, stack = depth + 1 (node counts and
     #    depths from build_bvh, run stand-alone on these very primitives)
     _c("cloud1732", lambda b: cloud(b, 1732), 601, **BIG, expect=dict(lds_level=1, stack_depth=13), knobs=BVH),   # 1024 nodes

@@ -218,3 +218,28 @@ def test_lowering_enables_the_step_for_constant_isotropic_media_only():
     d = desc.contents
     d.materials[d.media[1 - dense].material].kind = RT_MAT_LAMBERTIAN
     assert not lowering_enables(desc)
+
+
+def test_lowering_answers_for_the_generated_ball_cases():
+    """tests/gen_scenes.py ball_*: 1 for every variant the step is meant to run on; 0 for three
+    media and for a noise texture; 1 for with_instance, where lowering says yes and the kernel
+    variant with instance chains has no ball waves (tests/test_gpu_ball_generated.py)."""
+    import gen_scenes as G
+    want = {v: True for v in G.BALL_QUALIFY}
+    want.update(three_media=False, noise_medium=False, with_instance=True)
+    assert set(want) == set(G.BALL_QUALIFY + G.BALL_DECLINE)
+    for v, w in want.items():
+        desc, _ = G.build(G.BY_NAME["ball_" + v])
+        d = desc.contents
+        assert lowering_enables(desc) == w, v
+        assert d.nprims > 64 and d.ninstances == (1 if v == "with_instance" else 0), v
+        # every medium an isotropic; of a constant texture (noise_medium's second apart), pairwise distinct, no 0 or 1
+        cols = []
+        for i in range(d.nmedia):
+            m = d.materials[d.media[i].material]
+            assert m.kind == 4
+            t = d.textures[m.texture]
+            if t.kind == 0:
+                cols.append(tuple(t.color))
+        assert len(cols) == d.nmedia - (v == "noise_medium") and len(set(cols)) == len(cols), v
+        assert all(0 < x < 1 for col in cols for x in col), v

@@ -135,6 +135,9 @@ media8_scan 0.268  media9_scan 0.247  media12_scan 0.328  media9_bvh 0.281  medi
 boundaries_scan 0.289  boundaries_bvh 0.307
 cell_two_dense 0.299  cell_two_equal 0.276  cell_near4 0.224  cell_near5 0.229  cell_near_inst_moving 0.216
 cell_dup_outside 0.268  cell_not_dense 0.315
+ball_one_medium 0.682  ball_dense_first 0.840  ball_dense_second 0.838  ball_in_fog_on_ground 1.000
+ball_full_cell 0.682  ball_thin 0.689  ball_negative_radius 0.678  ball_solid 0.678  ball_three_media 0.843
+ball_noise_medium 0.844  ball_with_instance 0.837  ball_camera_inside 1.000
 cloud1732 0.398  cloud1736 0.398  quad4095 0.250  quad4096 0.250  quad4095_cell_prescan 0.539
 cloud1800_cell_prescan 0.609  progression200 0.148
 chains_short 0.302  chains_long 0.336  image_rects 0.263  textures_by_kind 0.375
@@ -144,7 +147,7 @@ chains_short 0.302  chains_long 0.336  image_rects 0.263  textures_by_kind 0.375
 @pytest.mark.parametrize("case", G.CASES, ids=lambda c: c.name)
 def test_generated_case_is_not_vacuous(case, images):
     """The case's target is in view: the oracle image without it differs in at least one pixel.
-    Measured shares of differing pixels per case: VACUITY_SHARES above (0.107 to 0.714)."""
+    Measured shares of differing pixels per case: VACUITY_SHARES above (0.107 to 1.000)."""
     b = case.builder()
     assert b.t_prims or b.t_media or b.t_textures, "the case names no target"
     plain = O.render_desc(b.desc(plain=True), case.camera(), case_spec(case))[0]
@@ -260,7 +263,14 @@ def cell_choice(d):
     ("cell_near_inst_moving", 0, 4, 1), ("cell_dup_outside", 0, 4, 1),
     ("cell_not_dense", 1, 1, 1),                                        # 1 / 2 >= 0.45: only the second ball is deep
     ("quad4095_cell_prescan", 0, 1, 1), ("cloud1800_cell_prescan", 0, 1, 1),
-    ("boundaries_bvh", None, 0, 0)])                                    # no boundary is one plain sphere
+    ("boundaries_bvh", None, 0, 0),                                     # no boundary is one plain sphere
+    # the ball_* cases: the cell is the dense ball's (medium 1 where the second medium is listed first), with
+    # the shell as its one near primitive, the ground where there is no shell, RT_CELL_MAX in full_cell
+    ("ball_one_medium", 0, 1, 1), ("ball_dense_first", 0, 1, 1), ("ball_dense_second", 1, 1, 1),
+    ("ball_in_fog_on_ground", 0, 1, 2),                                 # (the scene-wide fog counts as deep: 12.5 < 15)
+    ("ball_full_cell", 0, 4, 1), ("ball_thin", 0, 1, 0), ("ball_negative_radius", 0, 1, 1), ("ball_solid", 0, 1, 1),
+    ("ball_three_media", 0, 1, 1), ("ball_noise_medium", 0, 1, 1), ("ball_with_instance", 0, 1, 1),
+    ("ball_camera_inside", 0, 4, 1)])
 def test_medium_cell_choice_of_the_cases(name, medium, nnear, deep):
     """RTNW_CELL=0 in tests/test_gpu_generated.py proves something only where the cell is taken,
     and no rt_stats field shows that: the choice is recomputed here from each descriptor by
@@ -271,6 +281,70 @@ def test_medium_cell_choice_of_the_cases(name, medium, nnear, deep):
     assert (got_medium, len(near), got_deep) == (medium, nnear, deep)
     if name == "cell_near_inst_moving":
         assert {d.prims[q].kind for q in near} == {G.SPHERE, G.MSPHERE, G.XY} and sum(d.prims[q].instance >= 0 for q in near) == 2
+    if name.startswith("ball_"):
+        bp = d.boundary_prims[d.media[got_medium].boundary_first]
+        assert d.media[got_medium].density == np.float32(G.BALL_DENSITY[name[5:]]) and abs(bp.p[3]) == G.BALL_R
+        assert d.nprims > 64 and d.ninstances == (1 if name == "ball_with_instance" else 0)
+        kinds = sorted(d.prims[q].kind for q in near)
+        if name in ("ball_full_cell", "ball_camera_inside"):   # the shell, a metal sphere, a moving sphere whose centres differ by more than its radius, a rect
+            assert kinds == [G.SPHERE, G.SPHERE, G.MSPHERE, G.XZ]
+            ms = [d.prims[q] for q in near if d.prims[q].kind == G.MSPHERE][0]
+            assert np.linalg.norm(np.subtract(list(ms.p)[3:6], list(ms.p)[0:3])) > ms.p[8] > 0
+        else:
+            assert kinds == [G.XZ if name == "ball_in_fog_on_ground" else G.SPHERE]
+
+
+def test_ball_cases_list_both_kinds():
+    assert sorted(c.name for c in G.CASES if c.name.startswith("ball_")) == sorted("ball_" + v for v in G.BALL_QUALIFY + G.BALL_DECLINE)
+    c = G.BY_NAME["ball_camera_inside"]   # its camera is inside the ball, the others' outside
+    assert np.linalg.norm(np.subtract(c.lookfrom, G.ball_centre("camera_inside"))) < 0.8 * G.BALL_R
+    assert all(np.linalg.norm(np.subtract(k.lookfrom, G.ball_centre(k.name[5:]))) > 2 * G.BALL_R
+               for k in G.CASES if k.name.startswith("ball_") and k is not c)
+
+
+def test_in_fog_on_ground_has_segments_the_cell_cannot_decide():
+    """ball_in_fog_on_ground exists for the `best_t < tsafe` rule of the fused in-ball step: a
+    segment that starts inside the ball and whose closest cell primitive (the ground, the only
+    one) lies beyond the ball's exit, with a sphere outside the cell or a fog scatter before it.
+    A float64 ray cast over the descriptor: origins uniform in the ball, directions uniform in the
+    unit ball (what an isotropic scatter leaves behind: material.h:147), the fog's free path
+    drawn as constant_medium.h:36 draws it.  At least 1 % of those segments must be such."""
+    c = G.BY_NAME["ball_in_fog_on_ground"]
+    d = G.build(c)[0].contents
+    medium, near, _ = cell_choice(d)
+    bp, fog = d.boundary_prims[d.media[medium].boundary_first], d.media[1 - medium]
+    cc, R = np.array(list(bp.p)[0:3], float), abs(bp.p[3])
+    assert near == [0] and d.prims[0].kind == G.XZ and fog.density < 0.1   # (the ground is primitive 0)
+    rng = np.random.default_rng(7)
+    n = 20000
+    v = rng.normal(size=(n, 3))
+    o = cc + R * rng.uniform(size=(n, 1)) ** (1 / 3) * v / np.linalg.norm(v, axis=1, keepdims=True)
+    w = rng.normal(size=(n, 3))
+    dirs = rng.uniform(size=(n, 1)) ** (1 / 3) * w / np.linalg.norm(w, axis=1, keepdims=True)
+
+    def sphere_t(centre, rad):   # the smallest root above t_min, inf where none
+        oc = o - centre
+        a, hb, k = (dirs * dirs).sum(1), (oc * dirs).sum(1), (oc * oc).sum(1) - rad * rad
+        disc = hb * hb - a * k
+        s = np.sqrt(np.maximum(disc, 0))
+        t0, t1 = (-hb - s) / a, (-hb + s) / a
+        t = np.where(t0 > 1e-3, t0, np.where(t1 > 1e-3, t1, np.inf))
+        return np.where(disc > 0, t, np.inf)
+    t_exit = sphere_t(cc, R)
+    g = list(d.prims[0].p)
+    tg = (g[4] - o[:, 1]) / dirs[:, 1]
+    x, z = o[:, 0] + tg * dirs[:, 0], o[:, 2] + tg * dirs[:, 2]
+    tg = np.where((tg > 1e-3) & (x > g[0]) & (x < g[1]) & (z > g[2]) & (z < g[3]), tg, np.inf)
+    others = np.full(n, np.inf)
+    for q in range(1, d.nprims):
+        assert d.prims[q].kind == G.SPHERE
+        others = np.minimum(others, sphere_t(np.array(list(d.prims[q].p)[0:3], float), abs(d.prims[q].p[3])))
+    fog_t = -(1.0 / fog.density) * np.log(rng.uniform(size=n)) / np.linalg.norm(dirs, axis=1)   # the camera and the ball are inside the fog
+    undecided = np.isfinite(tg) & (tg > t_exit) & (np.minimum(others, fog_t) < tg)
+    print(f"ball_in_fog_on_ground: ground beyond the exit {np.mean(np.isfinite(tg) & (tg > t_exit)):.3f}, with a sphere before "
+          f"it {np.mean(undecided & (others < tg)):.3f}, a fog scatter before it {np.mean(undecided & (fog_t < tg)):.3f}, "
+          f"either {undecided.mean():.3f}")
+    assert undecided.mean() >= 0.01
 
 
 def test_every_case_with_a_medium_cell_compares_it():
