@@ -464,6 +464,58 @@ int rt_firefly_dev(int device, int nx, int ny, const float *color_dev, const flo
                    const float *moments_dev, const rt_firefly_params *fp, float *out_dev,
                    float *out_moments_dev, float *ratio_dev, void *stream);
 
+/* ------------------------------- ray queries on the caller's own rays */
+#define RT_HIT_MISS (-1)
+#define RT_HIT_INVALID (-2)
+typedef struct rt_ray {      /* 48 bytes */
+    float origin[3], t_min;
+    float dir[3],    t_max;  /* dir need not be unit length; t is in units of dir */
+    float time;              /* moving spheres (sphere.h:81-83); ignored without them */
+    float pad[3];            /* ignored */
+} rt_ray;
+typedef struct rt_hit {      /* 48 bytes */
+    int32_t prim;            /* index into rt_scene_desc.prims; RT_HIT_MISS -1; RT_HIT_INVALID -2 */
+    int32_t material;        /* that primitive's material index; -1 without a hit */
+    float t, depth;          /* hit parameter; t * |dir| (0, 0 without a hit) */
+    float normal[3];         /* the hit record's normal, as rt_render_features defines it; 0 without a hit */
+    float albedo[3];         /* the hit material's colour, as rt_render_features defines it; (1,1,1) without a hit */
+    int32_t pad[2];          /* written as 0 */
+} rt_hit;
+/* Closest hit.  hits[k] is what hitable_list::hit(r, t_min, t_max, rec) returns for rays[k]
+ * over the scene's surfaces, constant media skipped as rt_render_features skips them: the
+ * closest hit under each primitive's own acceptance rule — a sphere needs t_min < t < t_max
+ * (sphere.h:33), a rect accepts t_min <= t <= t_max (aarect.h:52) — with ties by the list's
+ * rule: a later rect wins a tie, a sphere never displaces an earlier hit at equal t.  A t_max
+ * of +inf, or at or above FLT_MAX, means the reference's MAXFLOAT.  prim is the index into
+ * rt_scene_desc.prims (the descriptor's list index, not a place in the device's arrays),
+ * material that primitive's material; normal and albedo are exactly rt_render_features'
+ * per-sample values, and depth is t * len(dir) as that pass computes it (the float32 product,
+ * len = sqrtf((x*x + y*y) + z*z)).
+ * Occlusion.  rt_occluded writes 1 exactly where rt_trace_rays reports prim >= 0, 0 where it
+ * reports a miss; its search may stop at the first accepted hit.
+ * Invalid rays.  A ray is invalid when origin, dir, time or t_min has a non-finite component,
+ * t_max is NaN, dir is (0, 0, 0), or the scene has moving spheres and time lies outside the
+ * scene's [time0, time1] (the moving spheres' boxes do not cover it).  It reports
+ * RT_HIT_INVALID (255 from rt_occluded) with the other fields as for a miss; the device tests
+ * every ray itself, the other rays of the call are not affected.
+ * Axis-parallel rays.  A ray with a direction component of exactly 0 is traced like any other.
+ * Where a rect is tested its result is outside the parity contract, as in the renders
+ * (DESIGN.md §2); on scenes of spheres only it is exact.
+ * Arguments, all checked before any HIP call, the scene last: RT_ERR_INVALID for n < 0 or
+ * n > 2^31 - 1; n == 0 is RT_OK and touches nothing, whatever the other arguments;
+ * RT_ERR_INVALID for null rays or a null output, then for a null scene; RT_ERR_UNSUPPORTED on
+ * a scene with a wide BVH (RTNW_BVH_WIDTH 4, 8, 8q) or when the library was linked without
+ * the trace unit.
+ * The host forms are synchronous and stage rays and results through device buffers kept with
+ * the scene, in batches of RTNW_TRACE_BATCH rays (env; default 2^20, at most 2^24); the result
+ * does not depend on the batch size.  *ms, when non-NULL, receives the kernels' HIP-event time.
+ * The _dev forms take device pointers (16-B aligned rays and hits), need no workspace and
+ * only enqueue on `stream` (hipStream_t, NULL = default). */
+int rt_trace_rays    (rt_scene *s, const rt_ray *rays, int64_t n, rt_hit *hits, double *ms);   /* host buffers, synchronous */
+int rt_trace_rays_dev(rt_scene *s, const rt_ray *rays_dev, int64_t n, rt_hit *hits_dev, void *stream);
+int rt_occluded      (rt_scene *s, const rt_ray *rays, int64_t n, uint8_t *out, double *ms);   /* 0 clear, 1 occluded, 255 invalid ray */
+int rt_occluded_dev  (rt_scene *s, const rt_ray *rays_dev, int64_t n, uint8_t *out_dev, void *stream);
+
 /* Diagnostic: the device's float transcendentals of the path on n host inputs (out: n
  * floats) — fn 0 the megakernel's sinf (texture.h:36, 55), 2 its asinf and 4 its
  * atan2f(a, b) (hitable.h:15-16), all restated from glibc (rt_libm.h); 1, 3, 5 ocml's

@@ -110,6 +110,7 @@ struct rt_scene : rtnw::SceneInfo {
     DevBuf counter;               // the work counter (64 B), then the statistics counters ...
     void *stats = nullptr;        // ... which start here
     DevBuf host_out;
+    DevBuf trace_ws;              // rt_trace_rays, rt_occluded: one batch of rays, then its results
     Events<3> ev;
     rt_scene() = default;
     ~rt_scene() {

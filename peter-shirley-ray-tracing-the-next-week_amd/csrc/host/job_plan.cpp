@@ -5,6 +5,7 @@
 #include "job_plan.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 namespace rtnw {
@@ -192,6 +193,15 @@ int plan_feature_batches(uint64_t npix, int spp, uint64_t pixel_bytes, uint64_t 
     if (npix * per >= 0x80000000ull) return fail(RT_ERR_INVALID, "rt_render_features: rectangle too large");
     *per_out = per;
     return RT_OK;
+}
+
+uint64_t plan_trace_batch(uint64_t n, const char *knob) {
+    uint64_t per = RT_TRACE_BATCH;
+    if (knob) {
+        const long long v = std::atoll(knob);
+        if (v > 0) per = std::min<uint64_t>((uint64_t)v, RT_TRACE_BATCH_MAX);
+    }
+    return std::max<uint64_t>(1, std::min(per, n));
 }
 
 }  // namespace rtnw

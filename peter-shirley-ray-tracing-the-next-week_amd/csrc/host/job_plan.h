@@ -63,5 +63,14 @@ BatchLaunch plan_batch(const BatchPlan &pl, uint64_t b, uint64_t npix, int spp, 
 // The feature pass's own rule: batches of *per whole samples of every pixel within slab_bytes.
 int plan_feature_batches(uint64_t npix, int spp, uint64_t pixel_bytes, uint64_t slab_bytes, uint64_t *per);
 
+// Ray queries (capi_trace.cpp): the legal ray counts (one launch takes fewer than 2^31 lanes, and
+// a batch is at most the whole call), and the rays per batch of a host-side call: `knob` is
+// RTNW_TRACE_BATCH's text (NULL or not a positive number: RT_TRACE_BATCH rays), clipped to
+// 1..RT_TRACE_BATCH_MAX and to n.  n >= 1.
+#define RT_TRACE_BATCH (1ull << 20)       // 48 MiB of rays and as much of hits
+#define RT_TRACE_BATCH_MAX (1ull << 24)
+inline bool ray_count_ok(int64_t n) { return n >= 0 && n <= 0x7FFFFFFFll; }
+uint64_t plan_trace_batch(uint64_t n, const char *knob);
+
 }  // namespace rtnw
 #pragma GCC visibility pop

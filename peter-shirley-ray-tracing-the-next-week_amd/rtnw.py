@@ -143,6 +143,38 @@ FIREFLY_DEFAULTS = dict(demodulate=1, radius=2, min_similar=3, k=8.0, floor=0.01
                         sigma_albedo=0.25)
 
 
+class RtRay(ctypes.Structure):   # 48 bytes
+    _fields_ = [("origin", ctypes.c_float * 3), ("t_min", ctypes.c_float), ("dir", ctypes.c_float * 3),
+                ("t_max", ctypes.c_float), ("time", ctypes.c_float), ("pad", ctypes.c_float * 3)]
+
+
+class RtHit(ctypes.Structure):   # 48 bytes
+    _fields_ = [("prim", ctypes.c_int32), ("material", ctypes.c_int32), ("t", ctypes.c_float), ("depth", ctypes.c_float),
+                ("normal", ctypes.c_float * 3), ("albedo", ctypes.c_float * 3), ("pad", ctypes.c_int32 * 2)]
+
+
+RT_HIT_MISS, RT_HIT_INVALID = -1, -2
+RT_OCCLUDED_INVALID = 255
+# rt_ray and rt_hit as numpy records (the ctypes structures' layout)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("dir", np.float32, 3), ("t_max", np.float32),
+                      ("time", np.float32), ("pad", np.float32, 3)])
+HIT_DTYPE = np.dtype([("prim", np.int32), ("material", np.int32), ("t", np.float32), ("depth", np.float32),
+                      ("normal", np.float32, 3), ("albedo", np.float32, 3), ("pad", np.int32, 2)])
+
+
+def pack_rays(origin, dir, t_min=0.001, t_max=np.inf, time=0.0) -> np.ndarray:
+    """rt_ray records ([n] RAY_DTYPE) from origins and directions [n, 3] (either may be one
+    vector for all) and t_min, t_max and time, scalars or [n]."""
+    o = np.asarray(origin, np.float32).reshape(-1, 3)
+    d = np.asarray(dir, np.float32).reshape(-1, 3)
+    n = max(len(o), len(d), *(np.size(x) for x in (t_min, t_max, time)))
+    rays = np.zeros(n, RAY_DTYPE)
+    rays["origin"], rays["dir"] = o, d
+    for name, x in (("t_min", t_min), ("t_max", t_max), ("time", time)):
+        rays[name] = np.asarray(x, np.float32).reshape(-1)
+    return rays
+
+
 class RtCheckpoint(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("nx", ctypes.c_int32),
                 ("ny", ctypes.c_int32), ("samples_done", ctypes.c_uint32), ("max_depth", ctypes.c_int32),
@@ -205,6 +237,14 @@ def lib():
             "rt_firefly_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, P(RtFireflyParams), ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_trace_rays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                             P(ctypes.c_double)]),
+            "rt_trace_rays_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+            "rt_occluded": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           P(ctypes.c_double)]),
+            "rt_occluded_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
             "rt_device_alloc": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, P(ctypes.c_void_p)]),
             "rt_device_free": (ctypes.c_int, [ctypes.c_void_p]),
             "rt_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
@@ -237,11 +277,12 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass, the denoiser and the firefly clamp
+        # the feature pass, the denoiser, the firefly clamp and the ray queries
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
                     "rt_copy_to_device",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
-                    "rt_firefly", "rt_firefly_dev"}
+                    "rt_firefly", "rt_firefly_dev",
+                    "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -516,6 +557,44 @@ class Scene:
         normal.xyz, depth) into device memory, enqueued on the stream."""
         _check(lib().rt_render_features_dev(self.handle, ctypes.byref(cam.desc), ctypes.byref(params), x0, y0, w, h,
                                             ctypes.c_void_p(guides_dev_ptr), ctypes.c_void_p(stream_ptr)))
+
+    @staticmethod
+    def _rays(rays) -> np.ndarray:
+        r = np.ascontiguousarray(rays)
+        if r.dtype != RAY_DTYPE:
+            raise TypeError("rays must be rt_ray records (RAY_DTYPE; see pack_rays)")
+        return r.reshape(-1)
+
+    def trace_rays(self, rays, timing: bool = False):
+        """Closest hit of each rt_ray record (pack_rays) by rt_trace_rays: a dict of numpy
+        arrays, `prim` and `material` [n] int32 (prim -1: miss, -2: invalid ray), `t` and
+        `depth` [n], `normal` and `albedo` [n, 3] float32, and `pad` [n, 2] int32 (zeros).
+        timing: also the kernels' HIP-event time in ms."""
+        r = self._rays(rays)
+        hits = np.zeros(len(r), HIT_DTYPE)
+        ms = ctypes.c_double(0.0)
+        _check(lib().rt_trace_rays(self.handle, r.ctypes.data, len(r), hits.ctypes.data, ctypes.byref(ms)))
+        out = {k: np.ascontiguousarray(hits[k]) for k in HIT_DTYPE.names}
+        return (out, ms.value) if timing else out
+
+    def occluded(self, rays, timing: bool = False):
+        """rt_occluded: [n] uint8, 1 where the ray hits a surface between its t_min and t_max,
+        0 where not, 255 for an invalid ray."""
+        r = self._rays(rays)
+        out = np.zeros(len(r), np.uint8)
+        ms = ctypes.c_double(0.0)
+        _check(lib().rt_occluded(self.handle, r.ctypes.data, len(r), out.ctypes.data, ctypes.byref(ms)))
+        return (out, ms.value) if timing else out
+
+    def trace_rays_dev(self, rays_dev_ptr: int, n: int, hits_dev_ptr: int, stream_ptr: int = 0):
+        """rt_trace_rays_dev: n rt_ray records in device memory into n rt_hit records there."""
+        _check(lib().rt_trace_rays_dev(self.handle, ctypes.c_void_p(rays_dev_ptr), n, ctypes.c_void_p(hits_dev_ptr),
+                                       ctypes.c_void_p(stream_ptr)))
+
+    def occluded_dev(self, rays_dev_ptr: int, n: int, out_dev_ptr: int, stream_ptr: int = 0):
+        """rt_occluded_dev: n rt_ray records in device memory into n bytes there."""
+        _check(lib().rt_occluded_dev(self.handle, ctypes.c_void_p(rays_dev_ptr), n, ctypes.c_void_p(out_dev_ptr),
+                                     ctypes.c_void_p(stream_ptr)))
 
     def close(self):
         if self.handle:
