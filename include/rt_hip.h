@@ -248,6 +248,11 @@ typedef struct rt_stats {
     double ball_fused_declined;   /*   eligible lanes a trip of that step left to the generic stages (a cell
                                          primitive first, the cell undecided, or no scatter); both are 0 in a
                                          kernel variant without ball waves */
+    double empty_fast_samples;    /* RT_FLAG_COUNT: camera samples of provably empty pixels that the work claim
+                                         finished itself (no surface in reach, no medium scattered): counted in
+                                         samples and segments, never seen by the traversal; 0 with
+                                         RTNW_EMPTY_FAST=0 or in a render that leaves the feature off */
+    double empty_pixels;          /* job pixels flagged as provably empty for this render (0: feature off) */
 } rt_stats;
 
 typedef struct rt_scene rt_scene; /* opaque; owns device copies */

@@ -1406,7 +1406,9 @@ __device__ __forceinline__ void load_media(const RtKernelArgs &A, MediumRec *lds
 }
 
 // One medium's test (constant_medium.h:26-50) against the surface result.
-template <bool kCount, bool kInst = true>
+// kPlain: every medium of the scene is bounded by one plain sphere (the host checked), so the
+// other boundaries' code is left out (rt_kernel.hip refill).
+template <bool kCount, bool kInst = true, bool kPlain = false>
 __device__ __forceinline__ void medium_one(const RtKernelArgs &A, const MediumRec &M, int k, const Ray &r, const Recip &rd,
                                            const Recip &ra, uint64_t xk, bool &have, float &best_t,
                                            int &med_mat, LdsMediaConsts *mc, Counters &cnt) {
@@ -1416,7 +1418,7 @@ __device__ __forceinline__ void medium_one(const RtKernelArgs &A, const MediumRe
     float r1, r2;
     bool ok;
     const float4 bm = M.mm;
-    if (md.y == 1 && (fbits(bm.x) & 0xff) == RT_PRIM_SPHERE && fbits(bm.z) < 0) {   // wave-uniform
+    if (kPlain || (md.y == 1 && (fbits(bm.x) & 0xff) == RT_PRIM_SPHERE && fbits(bm.z) < 0)) {   // wave-uniform
         // one sphere: both boundary calls (constant_medium.h:28-29) share the roots
         if (kCount) cnt.spheres++;
         const float4 sg = M.g0;

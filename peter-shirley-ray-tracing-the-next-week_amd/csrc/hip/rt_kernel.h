@@ -100,6 +100,10 @@ struct RtKernelArgs {
     // the media's constant albedos in list order (scene_lower.cpp ball_fast_media)
     int ball_fast;
     float ball_alb[2][3];
+    // one bit per job pixel (bit p & 31 of word p >> 5): no primary ray of the pixel can reach a
+    // surface, and the render is one whose such samples refill may finish itself (rt_kernel.hip
+    // refill, empty_pixels.cpp); null: none is (RTNW_EMPTY_FAST=0, or a condition fails)
+    const uint32_t *empty_bits;
 };
 
 // mode: 0 plain, 1 count, 2 profile, RT_LAUNCH_FOLD the plain right-fold variant (width 2 only)

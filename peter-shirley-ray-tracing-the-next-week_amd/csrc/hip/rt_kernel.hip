@@ -140,6 +140,13 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     // mostly start outside the ball, its lockstep tests cost every lane (c4 +3.8 %)
     constexpr bool kBall = kMedia && !kInst && kFeat != RT_FEAT_ALL && kLds && kWidth == 2 && !kFold;
     constexpr bool kCell = kBall;
+    // refill finishes the samples of provably empty pixels itself (RtKernelArgs.empty_bits) in the
+    // plain width-2 media variant: final()'s, which also runs the scenes with no feature at all.
+    // (With the instance chains' code the block spilled, 12 B of scratch per lane in cornell_box's
+    // LDS variant; in the random scenes' variant, whose benchmark camera has a lens and never
+    // uses it, its mere presence cost c3 1.2 %: profiles/r16.  The other variants ignore the bits,
+    // their samples take the generic stages, and their refill is the one they had.)
+    constexpr bool kEmptyFast = kFeat == RT_FEAT_MEDIA && kWidth == 2 && !kFold;
     // the LDS node layout (rt_device.h RtSplit): dword planes in the media variants (final()),
     // float4 planes otherwise, as each measured fastest
     constexpr int kSplit = rt_lds_split(kSearch, kFeat, kWidth);
@@ -255,6 +262,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     uint32_t best_prim = 0xFFFFFFFFu;
 
     Counters cnt;
+    uint64_t cnt_empty = 0;   // (kCount) samples refill finished itself (rt_stats.empty_fast_samples)
     uint64_t prof[5] = {0, 0, 0, 0, 0};   // claim, traverse, media, shade, of which scatter branches
     uint64_t prof_iters = 0;              // (kProf) this wave's loop iterations
     uint64_t fast_trips = 0, fast_cycles = 0;   // (kProf) the fused in-ball step's trips and their cycles (part of traverse)
@@ -314,12 +322,15 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         }
         const uint32_t n = min(64u, pool_end - pool_next);
         if (kProf) rt_items += n;
-        if (lane < n) {
+        const bool mine = lane < n;
+        uint32_t c = 0, pj = 0;
+        uint64_t K = 0;
+        float cu = 0.f, cv = 0.f;
+        if (mine) {
             // item -> (sample chunk c, job pixel p): the job's first ndeep pixels (capi_render.cpp:
             // those whose primary rays enter a dense medium) have all their chunks first,
             // sample-major, then the other pixels' (RtKernelArgs.ndeep)
             const uint32_t it = pool_next + lane;
-            uint32_t c, pj;
             if (it < A.ndeep_items) {
                 c = it / A.ndeep;
                 pj = it - c * A.ndeep;
@@ -328,23 +339,115 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                 c = i2 / nb;
                 pj = A.ndeep + (i2 - c * nb);
             }
-            pre_cp[lane] = make_uint2(c, pj);
             const uint32_t xy = A.job_xy[pj];
             const int x = (int)(xy & 0xFFFFu), j = A.ny - 1 - (int)(xy >> 16);
             // the pixel key in uint32_t: j * nx passes INT_MAX in the upper half of a 65535-wide frame
-            const uint64_t K = sample_key(skey, (uint32_t)j * (uint32_t)A.nx + (uint32_t)x, c * (uint32_t)A.chunk + A.sample_offset);
+            K = sample_key(skey, (uint32_t)j * (uint32_t)A.nx + (uint32_t)x, c * (uint32_t)A.chunk + A.sample_offset);
             // main.cpp:305-306; A.rnx = RN(1/float(nx)) from the host (div_rn)
             const uint64_t x1 = lcg_step(K & kLcgM), x2 = lcg_step(x1);   // the sample's first two draws
-            const float cu = div_rn((float)((double)x + u48x(x1)), (float)A.nx, A.rnx);
-            const float cv = div_rn((float)((double)j + u48x(x2)), (float)A.ny, A.rny);
+            cu = div_rn((float)((double)x + u48x(x1)), (float)A.nx, A.rnx);
+            cv = div_rn((float)((double)j + u48x(x2)), (float)A.ny, A.rny);
+            pre_cp[lane] = make_uint2(c, pj);
             pre_key[lane] = K;
             pre_uv[lane] = make_float2(cu, cv);
+        }
+        // Samples of provably empty pixels (A.empty_bits, one bit per job pixel: no primary ray of
+        // the pixel can reach a surface; empty_pixels.cpp, which also checks that the lens radius
+        // is 0, chunk 1 and the rest of what follows relies on) are finished right here.  Such a
+        // sample is its camera ray (camera_finish with the zero lens offset: origin and direction
+        // are the pinhole's, whatever the disk draw), one medium_one per medium against
+        // t_max = FLT_MAX from the sample's own medium stream, and, unless a medium scatters, the
+        // miss radiance: the generic stages' own expressions, so images are bitwise unchanged.  A
+        // sample a medium scatters stays among the sample starts untouched and is served from
+        // scratch by the generic stages, as is one with a zero direction component (there the sign
+        // of x - (+-0) depends on the disk draw).  The others' items leave the slots: the survivors
+        // are compacted below.  (The item's values wait in the lane's own slot meanwhile: held in
+        // registers across the media they spilled.)
+        bool gone = false;
+        if (kEmptyFast && A.empty_bits != nullptr) {   // wave-uniform
+            const bool flagged = mine && ((A.empty_bits[pj >> 5] >> (pj & 31u)) & 1u) != 0u;
+            if (wballot(flagged) != 0ull) {
+                // (the arguments through a pointer of the block's own, read here: none of them is held
+                // in SGPRs from the iteration's start across the media, where they spilled)
+                KArgs *kb = opaque_kargs(ka);
+#define B (*(const RtKernelArgs *)kb)
+                const CamView C = load_camera(lds_cam);
+                Ray q;
+                q.o = C.org;
+                q.d = sub(add(add(C.llc, scale(cu, C.hor)), scale(cv, C.ver)), C.org);
+                q.time = C.t0;   // a closed shutter, or no boundary that moves
+                const bool el = flagged && q.d.x != 0.f && q.d.y != 0.f && q.d.z != 0.f;
+                if (el) {
+                    const bool nd = B.need_dlen != 0;
+                    const Recip rd = recip_of(nd ? len(q.d) : 0.f, nd);
+                    int mm = -1;
+                    const uint64_t c_sph = cnt.spheres, c_msp = cnt.mspheres, c_rec = cnt.rects, c_ins = cnt.instanced,
+                                   c_med = cnt.media;   // (kCount) a scattered sample is counted by the generic stages alone
+                    if constexpr (kMedia) {   // media_hit with nothing found yet
+                        const Recip ra = recip_of(dot(q.d, q.d), true);
+                        uint64_t xm = mix64(pre_key[lane] ^ 0xD1B54A32D192ED03ull) & kLcgM;   // Rng::start
+                        bool have = false;
+                        float bt = RT_FLT_MAX;
+                        const int nl = min(B.nmedia, RT_LDS_MEDIA);
+                        for (int k = 0; k < nl; ++k) {
+                            const MediumRec M = lds_medium_rec(lds_media, k);
+                            xm = lcg_step(xm);
+                            medium_one<kCount, kInst, true>(B, M, k, q, rd, ra, xm, have, bt, mm, (LdsMediaConsts *)&lds_mconst, cnt);
+                        }
+                        for (int k = RT_LDS_MEDIA; k < B.nmedia; ++k) {
+                            MediumRec M;
+                            M.md = B.media[k];
+                            M.g0 = B.bprims[M.md.x * 4 + 0];
+                            M.mm = B.bprims[M.md.x * 4 + 1];
+                            xm = lcg_step(xm);
+                            medium_one<kCount, kInst, true>(B, M, k, q, rd, ra, xm, have, bt, mm, (LdsMediaConsts *)&lds_mconst, cnt);
+                        }
+                    }
+                    if (mm < 0) {
+                        ShadeState st0;
+                        st0.kind = -1; st0.live = false; st0.wants_sphere = false; st0.tv = mk(0, 0, 0);
+                        // end_path of a first segment: de_nan(1 * e), then 0 + it
+                        V3 L = mul(mk(1, 1, 1), shade_emitted(B, false, q, rd, st0));
+                        if (!(L.x == L.x)) L.x = 0;
+                        if (!(L.y == L.y)) L.y = 0;
+                        if (!(L.z == L.z)) L.z = 0;
+                        L = add(mk(0, 0, 0), L);
+                        const uint2 cp = pre_cp[lane];
+                        float *sl = B.slab + ((size_t)cp.x * B.npix + cp.y) * RT_SLAB_FLOATS;
+                        sl[0] = L.x;
+                        sl[1] = L.y;
+                        sl[2] = L.z;
+                        gone = true;
+                        if (kCount) { cnt.samples++; cnt.segments++; cnt_empty++; }
+                    } else if (kCount) {
+                        cnt.spheres = c_sph; cnt.mspheres = c_msp; cnt.rects = c_rec; cnt.instanced = c_ins;
+                        cnt.media = c_med;
+                    }
+                }
+            }
+#undef B
+        }
+        const uint64_t keep = kEmptyFast ? wballot(mine && !gone) : 0ull;
+        if (kEmptyFast && wballot(gone) != 0ull) {   // the survivors move up, in order
+            const bool stay = mine && !gone;
+            const uint2 cp = pre_cp[lane];
+            const uint64_t k = pre_key[lane];
+            const float2 uv = pre_uv[lane];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (stay) {
+                const uint32_t e = lanes_below(keep);
+                pre_cp[e] = cp;
+                pre_key[e] = k;
+                pre_uv[e] = uv;
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         pre_head = 0;
-        pre_count = n;
+        pre_count = kEmptyFast ? (uint32_t)__popcll(keep) : n;
         pool_next += n;
     };
     // ---- stage 6's path pools (kBall; DESIGN.md §5c "ball waves") ----------------------
@@ -502,9 +605,16 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         }
         uint64_t need_mask = wballot(need);
         while (need_mask != 0ull) {
+            // (a refill may leave no sample start: a block of empty pixels it finished itself)
             if (pre_count == 0) {
-                if (!exhausted) refill();
-                if (pre_count == 0) break;
+                if constexpr (kEmptyFast) {
+                    if (exhausted) break;
+                    refill();
+                    if (pre_count == 0) continue;   // none left, or all of them finished there: look again
+                } else {
+                    if (!exhausted) refill();
+                    if (pre_count == 0) break;
+                }
             }
             const uint32_t rank = lanes_below(need_mask);
             if (need && rank < pre_count) {
@@ -1043,6 +1153,11 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     if (kCount && kBall && lane == 0)
         for (int k = 0; k < RT_BALL_N; ++k)
             if (cnt.ball[k]) atomicAdd(&A.stats[RT_STAT_BALL + k], (unsigned long long)cnt.ball[k]);
+    if (kCount) {
+        uint64_t x = cnt_empty;
+        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off);
+        if (lane == 0 && x) atomicAdd(&A.stats[RT_STAT_EMPTY], (unsigned long long)x);
+    }
     if (kCount) {
         uint64_t v[RT_CNT_N] = {cnt.samples, cnt.segments, cnt.nodes, cnt.spheres, cnt.mspheres, cnt.rects,
                                 cnt.instanced, cnt.media, cnt.shades, cnt.noise};

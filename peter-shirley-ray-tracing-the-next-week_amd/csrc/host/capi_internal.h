@@ -13,6 +13,7 @@
 #include "../hip/rt_kernel.h"
 #include "scene_lower.h"
 #include "job_plan.h"
+#include "empty_pixels.h"
 
 inline int fail(int code, const std::string &msg) { return rt_internal_fail(code, msg); }
 inline int hip_fail(hipError_t e, const char *what) {
@@ -102,6 +103,12 @@ struct rt_scene : rtnw::SceneInfo {
     uint32_t job_ndeep = 0;                 // the job's first job_ndeep pixels are the deep ones (prepare_job)
     uint32_t npix = 0;
     DevBuf job_xy, job_out;       // the job's pixel lists (both have room for the same number of pixels)
+    // the tile job's provably empty pixels, one bit per job pixel (empty_pixels.cpp), made with the
+    // lists and cached with them; job_empty: the bits describe the current job (a tile job of a
+    // scene and camera with the feature on), job_nflagged of them set
+    DevBuf empty_bits;
+    bool job_empty = false;
+    uint32_t job_nflagged = 0;
     DevBuf slab;
     DevBuf acc;                   // per-pixel running sums between sample batches
     DevBuf frame;                 // rt_render_adaptive: the frame's sums, moments, counts and flags ...

@@ -88,7 +88,10 @@ int prepare_job(rt_scene *s, const int32_t *tiles, int ntiles, int nx, int ny, c
     key.push_back(nx);
     key.push_back(ny);
     key.push_back(deep ? 1 : 0);
-    if (deep) {
+    // the empty-pixel bits depend on the camera too (and on whether it leaves the feature on)
+    const bool empty = rtnw::empty_fast_scene_ok(*s, cam);
+    key.push_back(empty ? 1 : 0);
+    if (deep || empty) {
         const float *cf[4] = {cam->origin, cam->lower_left_corner, cam->horizontal, cam->vertical};
         for (const float *f : cf)
             for (int k = 0; k < 3; k++) { int32_t b; std::memcpy(&b, &f[k], 4); key.push_back(b); }
@@ -109,6 +112,22 @@ int prepare_job(rt_scene *s, const int32_t *tiles, int ntiles, int nx, int ny, c
     HIP_TRY(hipMemcpy(s->job_out.p, oi.data(), oi.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     s->npix = (uint32_t)xy.size();
     s->job_ndeep = ndeep;
+    s->job_empty = false;
+    s->job_nflagged = 0;
+    if (empty) {
+        // once per job and camera, outside any timed step (RTNW_TRACE prints its time)
+        rtnw::PhaseTrace trace{"rt_render_tiles"};
+        std::vector<uint32_t> bits;
+        size_t nflagged = 0;
+        const bool ok = rtnw::empty_pixel_bits(*s, cam, nx, ny, xy.data(), xy.size(), &bits, &nflagged);
+        trace("empty pixels");
+        if (ok && nflagged > 0) {   // (none flagged: the kernel runs as without the bits)
+            if (int rc = s->empty_bits.reserve(bits.size() * sizeof(uint32_t))) return rc;
+            HIP_TRY(hipMemcpy(s->empty_bits.p, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            s->job_empty = true;
+            s->job_nflagged = (uint32_t)nflagged;
+        }
+    }
     s->job_tiles = key;
     return RT_OK;
 }
@@ -127,6 +146,7 @@ int prepare_job_slots(rt_scene *s, const JobSlots &js, int nx, int ny, hipStream
     for (uint32_t i = 0; i < js.n; i++)
         if ((int)(js.xy[i] & 0xFFFFu) >= nx || (int)(js.xy[i] >> 16) >= ny) return fail(RT_ERR_INVALID, "job pixel outside the image");
     s->job_tiles.clear();
+    s->job_empty = false;
     if (int rc = reserve_job_lists(s, js.n)) return rc;
     HIP_TRY(hipMemcpyAsync(s->job_xy.p, js.xy, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(s->job_out.p, js.slot, (size_t)js.n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
@@ -168,6 +188,9 @@ int read_counters(rt_scene *s, bool count, bool prof, double items, rt_stats *st
         HIP_TRY(hipMemcpy(b, (unsigned long long *)s->stats + RT_STAT_BALL, sizeof b, hipMemcpyDeviceToHost));
         stats->ball_fused_scatters = (double)b[RT_BALL_FUSED];
         stats->ball_fused_declined = (double)b[RT_BALL_DECLINED];
+        unsigned long long ef = 0;
+        HIP_TRY(hipMemcpy(&ef, (unsigned long long *)s->stats + RT_STAT_EMPTY, sizeof ef, hipMemcpyDeviceToHost));
+        stats->empty_fast_samples = (double)ef;
         if (std::getenv("RTNW_TRACE")) {   // diagnostics only
             std::fprintf(stderr,
                          "rtnw ball waves: iterations %llu, live lanes / iteration %.1f, traversal rounds / iteration %.2f, "
@@ -371,6 +394,11 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     a.wave_log = (unsigned long long *)wave_log.p;
     a.fold = fold ? (float4 *)s->fold.p : nullptr;
     a.fold_stride = (uint32_t)fold_lanes;
+    // refill finishes the samples of the job's empty pixels itself (rt_kernel.hip): a tile job of a
+    // scene and camera that allow it (prepare_job, empty_pixels.cpp), one sample per work item (the
+    // item is then the sample), no hit before the origin, not the right fold
+    const bool empty_fast = s->job_empty && rtnw::empty_fast_render_ok(p->t_min, chunk, p->flags, !js);
+    a.empty_bits = empty_fast ? (const uint32_t *)s->empty_bits.p : nullptr;
 
     // vec3::operator/= (vec3.h:134-141): col *= float(1.0 / ns)
     const uint32_t ns_total = sum_in ? p->sample_offset + (uint32_t)p->spp : (uint32_t)p->spp;
@@ -441,6 +469,7 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
         stats->scan_groups = s->scan ? (double)s->ngroups : 0.0;
         stats->prescan = (double)s->nprescan;
         stats->stack_depth = (double)(s->lds_nodes ? s->stack_depth : s->bvh_width >= 8 ? RT_STACK_DEPTH_W8 : RT_STACK_DEPTH);
+        stats->empty_pixels = a.empty_bits ? (double)s->job_nflagged : 0.0;
     }
     return RT_OK;
 }

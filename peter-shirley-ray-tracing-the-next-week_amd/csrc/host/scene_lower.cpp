@@ -484,6 +484,22 @@ int lower_scene(const rt_scene_desc *d, LoweredScene *out) {
     s.has_bvh = d->nprims > 0;
     s.nmedia = d->nmedia;
     s.deep_balls = dense_balls(d);
+    s.surf_boxes.resize((size_t)d->nprims * 6);
+    s.surf_spheres.resize((size_t)d->nprims * 5);
+    for (int i = 0; i < d->nprims; i++) {
+        const rt_prim &pr = d->prims[i];
+        prim_bounds(pr, d->instances, d->time0, d->time1, &s.surf_boxes[(size_t)i * 6], &s.surf_boxes[(size_t)i * 6 + 3]);
+        const bool plain = pr.kind == RT_PRIM_SPHERE && pr.instance < 0;
+        for (int k = 0; k < 3; k++) s.surf_spheres[(size_t)i * 5 + k] = plain ? pr.p[k] : 0.0f;
+        s.surf_spheres[(size_t)i * 5 + 3] = plain ? std::fabs(pr.p[3]) : -1.0f;
+        s.surf_spheres[(size_t)i * 5 + 4] = pr.kind == RT_PRIM_SPHERE ? std::fabs(pr.p[3])
+                                            : pr.kind == RT_PRIM_MOVING_SPHERE ? std::fabs(pr.p[8]) : 0.0f;
+    }
+    for (int i = 0; i < d->nmedia; i++) {
+        const rt_medium &m = d->media[i];
+        const rt_prim &bp = d->boundary_prims[m.boundary_first];
+        s.media_plain = s.media_plain && m.boundary_count == 1 && bp.kind == RT_PRIM_SPHERE && bp.instance < 0;
+    }
     s.bvh_depth = bvh.depth;
     s.nnodes = (int)bvh.node_count();
     s.bvh_width = bvh.width;

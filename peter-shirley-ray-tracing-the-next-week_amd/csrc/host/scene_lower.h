@@ -37,6 +37,12 @@ struct SceneInfo {
     bool has_specular = false; // a metal or dielectric material exists
     float time0 = 0, time1 = 1;
     std::vector<float> deep_balls;          // dense media's boundary balls (cx, cy, cz, r)
+    // what the empty-pixel classifier reads (empty_pixels.cpp): every surface primitive's padded
+    // world box (prim_bounds: lo xyz, hi xyz), and five floats per primitive: for a plain sphere
+    // (no instance chain, not moving) its centre and |radius|, radius -1 for every other
+    // primitive; then |radius| for a sphere of any kind, 0 for a rectangle
+    std::vector<float> surf_boxes, surf_spheres;
+    bool media_plain = true;   // every medium is bounded by one plain sphere (none: true)
 };
 
 // The scene's arrays share one image, uploaded by one copy into one device allocation: each

@@ -163,7 +163,8 @@ enum {
     RT_STAT_PROF = RT_CNT_N, RT_STAT_WAVE = RT_CNT_N + 4, RT_STAT_TIME = RT_CNT_N + 9, RT_STAT_SHADE = RT_CNT_N + 16,
     RT_STAT_BALL = RT_CNT_N + 20,   // RT_FLAG_COUNT, the ball waves (rt_kernel.hip stage 6): RT_BALL_*
     RT_STAT_SAMPLER = RT_CNT_N + 30,   // RT_FLAG_COUNT, the shading stage's rejection sampler: RT_SAMPLER_*
-    RT_STATS_LEN = RT_CNT_N + 34
+    RT_STAT_EMPTY = RT_CNT_N + 34,     // RT_FLAG_COUNT: samples of empty pixels finished at the work claim (lane-level)
+    RT_STATS_LEN = RT_CNT_N + 35
 };
 // ball-wave counters: ball-wave iterations, their live lanes and traversal rounds summed over
 // them, segments the medium cell decided (in ball waves), paths a normal wave could not push

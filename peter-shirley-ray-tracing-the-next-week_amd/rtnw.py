@@ -103,7 +103,7 @@ class RtStats(ctypes.Structure):
         "batches", "lds_level", "stack_depth", "scan_groups", "prescan", "wave_exhaust_first_us",
         "wave_exhaust_last_us", "wave_end_first_us", "wave_end_mean_us", "wave_end_last_us",
         "wave_shade_passes", "wave_shade_kinds", "lane_scatters", "cycles_scatter", "ball_fused_scatters",
-        "ball_fused_declined")]
+        "ball_fused_declined", "empty_fast_samples", "empty_pixels")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -13,7 +13,7 @@ build_one() {
       -Icsrc/hip -munsafe-fp-atomics -cuid=rt_kernel $defs -c "${RT_SRC:-csrc/hip/rt_kernel.hip}" -o ../variants/$name/rt_kernel.o \
       -Rpass-analysis=kernel-resource-usage 2> ../variants/$name/resource.txt
   /opt/rocm/bin/hipcc -shared --offload-arch=gfx950 -o ../variants/$name/librt_hip.so ../variants/$name/rt_kernel.o \
-      build/capi_scene.o build/capi_render.o build/capi_adaptive.o build/capi_post.o build/capi_util.o build/scene_lower.o build/job_plan.o build/bvh.o build/flatten.o build/rtnw.o build/png.o build/dist.o -lz -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+      build/capi_scene.o build/capi_render.o build/capi_adaptive.o build/capi_post.o build/capi_util.o build/scene_lower.o build/job_plan.o build/empty_pixels.o build/bvh.o build/flatten.o build/rtnw.o build/png.o build/dist.o -lz -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 }
 pids=()
 names=()
