@@ -521,6 +521,62 @@ int rt_trace_rays_dev(rt_scene *s, const rt_ray *rays_dev, int64_t n, rt_hit *hi
 int rt_occluded      (rt_scene *s, const rt_ray *rays, int64_t n, uint8_t *out, double *ms);   /* 0 clear, 1 occluded, 255 invalid ray */
 int rt_occluded_dev  (rt_scene *s, const rt_ray *rays_dev, int64_t n, uint8_t *out_dev, void *stream);
 
+/* ------------------- radiance queries: the path-traced colour of the caller's own rays */
+#define RT_RADIANCE_MAX_SKIP 192   /* the reach of the kernel's drand48 jump table (RT_LCG_JUMPS - 1) */
+typedef struct rt_path_ray {      /* 48 bytes, 16-B aligned in the _dev forms */
+    float origin[3], time;        /* time: moving spheres (sphere.h:81-83) */
+    float dir[3];                 /* need not be unit length */
+    uint32_t skip;                /* draws of the sample's stream already spent by the caller, 0..RT_RADIANCE_MAX_SKIP */
+    uint32_t pixel, sample;       /* the stream: sample_key(p->seed, pixel, sample), DESIGN.md §3 */
+    uint32_t pad[2];              /* ignored */
+} rt_path_ray;
+typedef struct rt_radiance {      /* 16 bytes */
+    float rgb[3];                 /* de_nan(color(ray, world, 0)), main.cpp:25-46, 232-242 */
+    int32_t status;               /* 0, or RT_HIT_INVALID */
+} rt_radiance;
+/* Result.  out[k].rgb is what the megakernel's default (forward-throughput) path computes for
+ * one sample whose first segment is rays[k]: the same stages, t_min, max_depth, background and
+ * de_nan as a render's sample.  It is the value a work item adds to its partial sum, before
+ * any sum over samples or mean: the one-sample work item's own sum 0 + de_nan(color(...)), so
+ * a component that is -0 comes back +0, as it does from every render.
+ * Main stream.  The sample's drand48 stream is restarted at the key of
+ * (p->seed, pixel, sample) and advanced by `skip` draws before the first scatter draws from it.
+ * Medium stream.  The sample's medium stream starts at its usual key, derived from the same
+ * (p->seed, pixel, sample), with segment 0.  `skip` does not affect it.
+ * Key fields are data.  pixel and sample are any uint32_t; nothing relates them to a frame.
+ * Parameters used from p: max_depth, t_min, background, seed.  nx, ny, spp, chunk and
+ * sample_offset are ignored.  Any flag is RT_ERR_INVALID (there are no right-fold, counting or
+ * profiling forms of the query).
+ * The ray-tracing identity (the contract).  If rays[k] is the ray camera::get_ray returns for
+ * sample `sample` of pixel key `pixel` (the uint32_t j * nx + x of rt_render_params' limits),
+ * and skip is the number of draws that sample spent before color(), then out[k].rgb is bitwise
+ * that pixel of rt_render_tile with spp = 1, sample_offset = sample and the same seed,
+ * max_depth, t_min and background.  The draws spent are 2 jitter draws (main.cpp:305-306), 2
+ * per lens-disk candidate including the accepted one (camera.h:49-56, drawn even when the lens
+ * radius is 0) and 1 time draw: 5 + 2 * (rejected candidates).
+ * skip range.  0..RT_RADIANCE_MAX_SKIP; a larger skip makes that ray invalid.
+ * Invalid rays.  A ray is invalid when origin, dir or time has a non-finite component, dir is
+ * (0, 0, 0), the scene has moving spheres and time lies outside the scene's [time0, time1], or
+ * skip > RT_RADIANCE_MAX_SKIP.  Its record comes back (0, 0, 0, RT_HIT_INVALID); it is never
+ * traced; the device tests every ray itself, and the other rays of the call are not affected.
+ * Axis-parallel rays are traced like any other, with rt_trace_rays' caveat on rects.
+ * Result independence.  A ray's record depends only on its rt_path_ray, the scene and p: not on
+ * its position in the call, on n, or on the host form's batches.
+ * Arguments, all checked before any HIP call, the scene last, in this order: RT_ERR_INVALID
+ * for n < 0 or n > 2^31 - 1; n == 0 is RT_OK and touches nothing, whatever the other
+ * arguments; RT_ERR_INVALID for a null p, rays or out, max_depth < 0, a non-finite t_min, a
+ * background outside RT_BG_* or any flag; RT_ERR_INVALID for a null scene; RT_ERR_UNSUPPORTED
+ * on a scene with a wide BVH (RTNW_BVH_WIDTH 4, 8, 8q) or when the library was linked without
+ * the rays unit.
+ * The host form is synchronous and stages rays and records through device buffers kept with
+ * the scene, in batches of RTNW_RADIANCE_BATCH rays (env; default 2^20, at most 2^24); *ms,
+ * when non-NULL, receives the kernels' HIP-event time.  The _dev form takes device pointers
+ * (16-B aligned) and only enqueues on `stream` (hipStream_t, NULL = default); like the renders
+ * it uses the scene's work counter, so calls on one scene must not overlap each other or a
+ * render of that scene. */
+int rt_radiance_rays    (rt_scene *s, const rt_render_params *p, const rt_path_ray *rays, int64_t n, rt_radiance *out, double *ms);
+int rt_radiance_rays_dev(rt_scene *s, const rt_render_params *p, const rt_path_ray *rays_dev, int64_t n, rt_radiance *out_dev, void *stream);
+
 /* Diagnostic: the device's float transcendentals of the path on n host inputs (out: n
  * floats) — fn 0 the megakernel's sinf (texture.h:36, 55), 2 its asinf and 4 its
  * atan2f(a, b) (hitable.h:15-16), all restated from glibc (rt_libm.h); 1, 3, 5 ocml's

@@ -104,6 +104,14 @@ struct RtKernelArgs {
     // surface, and the render is one whose such samples refill may finish itself (rt_kernel.hip
     // refill, empty_pixels.cpp); null: none is (RTNW_EMPTY_FAST=0, or a condition fails)
     const uint32_t *empty_bits;
+    // the ray-source variants (rt_kernel.hip kRays, rt_hip.h rt_radiance_rays): the work items are
+    // nitems ray records (rt_path_ray, 3 x float4 each) and each finished item stores its
+    // rt_radiance (one float4) at its own index; rays_moving: the scene has moving spheres, whose
+    // boxes cover [rays_t0, rays_t1] only (a ray whose time lies outside is invalid)
+    const float4 *rays;
+    float4 *radiance;
+    int rays_moving;
+    float rays_t0, rays_t1;
 };
 
 // mode: 0 plain, 1 count, 2 profile, RT_LAUNCH_FOLD the plain right-fold variant (width 2 only)
@@ -112,6 +120,19 @@ typedef hipError_t (*RtFoldLaunch)(const RtKernelArgs *a, int grid, hipStream_t 
 extern "C" hipError_t rt_launch_megakernel(const RtKernelArgs *a, int grid, int mode, hipStream_t stream);
 // 1 when the library holds the fold unit (a library linked from rt_kernel.o alone does not)
 extern "C" int rt_megakernel_has_fold(void);
+// The ray-source variants (rt_kernel_rays.hip: RT_FEAT_ALL, width 2, one kernel per search mode).
+// launch: a->scan / a->lds_nodes select the search as in rt_launch_megakernel; a->bvh_width must
+// be 2.  plan: the persistent grid's workgroups per CU and their threads for the search mode (0
+// BVH in HBM, 1 BVH2 in LDS, 2 flat scan); for mode 1, 0 workgroups when the variant's LDS
+// (static arrays, node planes and stacks of stack_depth entries) does not fit the CU, so that
+// the host keeps the nodes in HBM.
+// capi_radiance.cpp reaches both through the table, which the unit's static initialiser fills
+// when it is linked in (a library linked without it: RT_ERR_UNSUPPORTED).
+struct RtRaysLaunch {
+    hipError_t (*launch)(const RtKernelArgs *a, int grid, hipStream_t stream);
+    hipError_t (*plan)(int search, int stack_depth, int *blocks_per_cu, int *block_threads);
+};
+extern "C" RtRaysLaunch rt_rays_launch;   // defined (empty) in capi_radiance.cpp
 // Resolve of one sample batch (capi_render.cpp): adds the batch's partial sums to each
 // pixel's running sum in sample order.  mode: RT_RESOLVE_* bits.
 #define RT_RESOLVE_FIRST 1    // the first batch: start from 0 (or, with SUM_IN, from out)

@@ -109,6 +109,15 @@ enum : int { PH_IDLE = 0, PH_TRAV = 1, PH_READY = 2, PH_PARK = 3 };
 // lane that writes an entry is the only one that reads it (no ball waves: paths stay in
 // their lane), so plain loads and stores in program order suffice.  The switch shares
 // the search mode's template argument so that the other variants keep their names.
+// kMode & 8 (kRays, rt_kernel_rays.hip): the ray-source variants behind rt_radiance_rays
+// (rt_hip.h).  A work item is one caller-supplied ray record (RtKernelArgs.rays,
+// 48 B: origin, time, direction, the draws already spent, the stream's pixel and sample
+// numbers) instead of a camera sample: refill makes the sample starts from the records (key,
+// stream position after the skipped draws, the validity test), the camera stage takes origin,
+// direction and time from the record and draws nothing, and a finished item stores its 16 B
+// (rgb, status) straight into RtKernelArgs.radiance: no slab, no resolve.  The stages between
+// are the shared ones, so a record that restates a camera sample returns that sample's
+// radiance bit for bit.  RT_FEAT_ALL, width 2, forward throughput only.
 // Kernel arguments re-read each loop iteration: the persistent
 // loop reads ~40 uniform arguments; held in SGPRs across it they overflowed the 102
 // addressable SGPRs, which the compiler spilled into the lanes of a VGPR (v_writelane
@@ -122,8 +131,17 @@ __device__ __forceinline__ KArgs *opaque_kargs(KArgs *p) {
     return p;
 }
 
+// The ray-source variants (kMode & 8) carry every feature's code and, unbounded, allocate
+// about 160 VGPRs: at the other variants' 4 waves per SIMD (128 VGPRs) they spilled 6 to 51 of
+// them to scratch.  They are built for 3 waves per SIMD (168 VGPRs, no scratch), and their
+// BVH2-in-LDS workgroup is 12 waves instead of 16 (a 16-wave workgroup is 4 per SIMD).
+#define RT_RAYS_WAVES_PER_SIMD 3
+#define RT_RAYS_LDS_BLOCK (RT_RAYS_WAVES_PER_SIMD * 4 * 64)
+constexpr int rt_mega_block(int mode) { return (mode & 3) == 1 ? ((mode & 8) ? RT_RAYS_LDS_BLOCK : RT_LDS_BLOCK) : RT_BLOCK; }
+constexpr int rt_mega_waves(int mode) { return (mode & 8) ? RT_RAYS_WAVES_PER_SIMD : RT_WAVES_PER_SIMD; }
+
 template <bool kCount, bool kProf, int kWidth, int kFeat, int kMode>
-__global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVES_PER_SIMD) void rt_megakernel(RtKernelArgs A_param) {
+__global__ __launch_bounds__(rt_mega_block(kMode), rt_mega_waves(kMode)) void rt_megakernel(RtKernelArgs A_param) {
     (void)A_param;   // read through ka (the same bytes: the kernarg segment holds A_param at offset 0)
     KArgs *ka = (KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
 #define A (*(const RtKernelArgs *)ka)
@@ -132,6 +150,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                    kMedia = (kFeat & RT_FEAT_MEDIA) != 0;
     constexpr int kSearch = kMode & 3;
     constexpr bool kFold = (kMode & 4) != 0;
+    constexpr bool kRays = (kMode & 8) != 0;
     constexpr bool kLds = kSearch == 1, kScan = kSearch == 2;
     // the ball waves (stage 6) and the medium cell that ends their paths' closest-hit searches
     // (stage 3): the media variant without instance chains (final(); a cell needs a medium
@@ -147,10 +166,13 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     // uses it, its mere presence cost c3 1.2 %: profiles/r16.  The other variants ignore the bits,
     // their samples take the generic stages, and their refill is the one they had.)
     constexpr bool kEmptyFast = kFeat == RT_FEAT_MEDIA && kWidth == 2 && !kFold;
+    // refill may take items out of the sample starts it makes (kEmptyFast: the samples it finished;
+    // kRays: the invalid rays, whose zero record it stores): the survivors are compacted
+    constexpr bool kCompact = kEmptyFast || kRays;
     // the LDS node layout (rt_device.h RtSplit): dword planes in the media variants (final()),
     // float4 planes otherwise, as each measured fastest
     constexpr int kSplit = rt_lds_split(kSearch, kFeat, kWidth);
-    constexpr int kBlock = kLds ? RT_LDS_BLOCK : RT_BLOCK;
+    constexpr int kBlock = rt_mega_block(kMode);
     __shared__ uint32_t lds_stack[kSearch ? 1 : RT_BLOCK / 64][kSearch ? 1 : (kWidth >= 8 ? RT_STACK_DEPTH_W8 : RT_STACK_DEPTH)][64];
     __shared__ CoopSlot lds_slots[kBlock / 64][64];
     __shared__ MediumRec lds_media[RT_LDS_MEDIA];
@@ -232,7 +254,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     const GlobalNodes gnodes{A.nodes};
     const LdsNodes<kSplit> lnodes{(const LdsF4 *)lds_dyn};
 
-    const uint64_t skey = seed_key(A.seed);   // per-launch part of the sample keys
+    const uint64_t skey = kRays ? 0 : seed_key(A.seed);   // per-launch part of the sample keys (kRays: made in refill)
     // wave-uniform claim pool, and the pre-made sample starts [pre_head, pre_head + pre_count)
     uint32_t pool_next = 0, pool_end = 0;
     bool exhausted = false;
@@ -326,7 +348,42 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         uint32_t c = 0, pj = 0;
         uint64_t K = 0;
         float cu = 0.f, cv = 0.f;
-        if (mine) {
+        bool gone = false;
+        if constexpr (kRays) {
+            // 64 ray records -> 64 sample starts.  The key is the record's own (pixel, sample) under
+            // the launch's seed; the main stream restarts there and jumps the record's `skip` draws
+            // (one table entry: skip <= RT_LCG_JUMPS - 1); the medium stream's key is derived from K
+            // where the sample starts (Rng::start), so it is not affected.  The slots hold (item, -),
+            // K and, in pre_uv's 8 bytes, the 48-bit stream position.  An invalid record (rt_hip.h:
+            // a non-finite origin, direction or time, a zero direction, a time outside a moving
+            // scene's span, a skip past the table) gets its zero record here and leaves the slots.
+            static_assert(RT_RADIANCE_MAX_SKIP == RT_LCG_JUMPS - 1, "rt_hip.h states the jump table's reach");
+            // (the arguments through a pointer of the block's own, and the seed's key made here: held
+            // in SGPRs from the kernel's start they were spilled to a VGPR's lanes)
+            KArgs *kb = opaque_kargs(ka);
+#define B (*(const RtKernelArgs *)kb)
+            if (mine) {
+                const uint32_t it = pool_next + lane;
+                const float4 q0 = B.rays[(size_t)it * 3 + 0], q1 = B.rays[(size_t)it * 3 + 1], q2 = B.rays[(size_t)it * 3 + 2];
+                const uint32_t skip = __float_as_uint(q1.w);
+                auto fin = [](float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; };
+                const bool ok = fin(q0.x) && fin(q0.y) && fin(q0.z) && fin(q0.w) && fin(q1.x) && fin(q1.y) && fin(q1.z) &&
+                                !(q1.x == 0.f && q1.y == 0.f && q1.z == 0.f) && skip <= (uint32_t)RT_RADIANCE_MAX_SKIP &&
+                                (!B.rays_moving || (q0.w >= B.rays_t0 && q0.w <= B.rays_t1));
+                if (ok) {
+                    K = sample_key(seed_key(B.seed), __float_as_uint(q2.x), __float_as_uint(q2.y));
+                    const uint64_t x = lcg_jump(K & kLcgM, jt[skip]);
+                    pre_cp[lane] = make_uint2(it, 0u);
+                    pre_key[lane] = K;
+                    pre_uv[lane] = make_float2(__uint_as_float((uint32_t)x), __uint_as_float((uint32_t)(x >> 32)));
+                } else {
+                    __builtin_nontemporal_store(F4v{0.f, 0.f, 0.f, __int_as_float(RT_HIT_INVALID)}, (F4v *)B.radiance + it);
+                    gone = true;
+                }
+            }
+#undef B
+        }
+        if (!kRays && mine) {
             // item -> (sample chunk c, job pixel p): the job's first ndeep pixels (capi_render.cpp:
             // those whose primary rays enter a dense medium) have all their chunks first,
             // sample-major, then the other pixels' (RtKernelArgs.ndeep)
@@ -363,7 +420,6 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         // of x - (+-0) depends on the disk draw).  The others' items leave the slots: the survivors
         // are compacted below.  (The item's values wait in the lane's own slot meanwhile: held in
         // registers across the media they spilled.)
-        bool gone = false;
         if (kEmptyFast && A.empty_bits != nullptr) {   // wave-uniform
             const bool flagged = mine && ((A.empty_bits[pj >> 5] >> (pj & 31u)) & 1u) != 0u;
             if (wballot(flagged) != 0ull) {
@@ -427,8 +483,8 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
             }
 #undef B
         }
-        const uint64_t keep = kEmptyFast ? wballot(mine && !gone) : 0ull;
-        if (kEmptyFast && wballot(gone) != 0ull) {   // the survivors move up, in order
+        const uint64_t keep = kCompact ? wballot(mine && !gone) : 0ull;
+        if (kCompact && wballot(gone) != 0ull) {   // the survivors move up, in order
             const bool stay = mine && !gone;
             const uint2 cp = pre_cp[lane];
             const uint64_t k = pre_key[lane];
@@ -447,7 +503,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         pre_head = 0;
-        pre_count = kEmptyFast ? (uint32_t)__popcll(keep) : n;
+        pre_count = kCompact ? (uint32_t)__popcll(keep) : n;
         pool_next += n;
     };
     // ---- stage 6's path pools (kBall; DESIGN.md §5c "ball waves") ----------------------
@@ -575,10 +631,14 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     // holds paths leaves its idle lanes for the next top
     auto retire_and_claim = [&](bool top) {
         if (phase == PH_IDLE && !finished && item != 0xFFFFFFFFu && s_cur == s_end) {
-            float *sl = A.slab + (size_t)item * RT_SLAB_FLOATS;   // 12 B per item
-            sl[0] = part.x;
-            sl[1] = part.y;
-            sl[2] = part.z;
+            if constexpr (kRays) {   // the ray's record: its one sample's radiance (0 + de_nan(L)), status 0
+                __builtin_nontemporal_store(F4v{part.x, part.y, part.z, __int_as_float(0)}, (F4v *)A.radiance + item);
+            } else {
+                float *sl = A.slab + (size_t)item * RT_SLAB_FLOATS;   // 12 B per item
+                sl[0] = part.x;
+                sl[1] = part.y;
+                sl[2] = part.z;
+            }
             item = 0xFFFFFFFFu;
         }
         bool need = phase == PH_IDLE && !finished && item == 0xFFFFFFFFu;
@@ -607,7 +667,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         while (need_mask != 0ull) {
             // (a refill may leave no sample start: a block of empty pixels it finished itself)
             if (pre_count == 0) {
-                if constexpr (kEmptyFast) {
+                if constexpr (kCompact) {
                     if (exhausted) break;
                     refill();
                     if (pre_count == 0) continue;   // none left, or all of them finished there: look again
@@ -629,6 +689,11 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
                 s_cur = (int)(c * (uint32_t)A.chunk);
                 s_end = min(s_cur + A.chunk, A.ns);
                 part = mk(0, 0, 0);
+                if constexpr (kRays) {   // the item is the ray, its one sample
+                    item = cp.x;
+                    s_cur = 0;
+                    s_end = 1;
+                }
             }
             const uint32_t took = min((uint32_t)__popcll(need_mask), pre_count);
             pre_head += took;
@@ -640,6 +705,14 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     // a camera sample (main.cpp:305-308, camera.h:41-56): the sample's stream and
     // jitter, then (after the lens-disk point) the ray
     auto camera_begin = [&](bool starting, float &cu_, float &cv_) {
+        if constexpr (kRays) {   // the record's stream, where its skipped draws end (refill); no jitter
+            if (starting) {
+                g.start(pre_k, kMedia);
+                g.x = ((uint64_t)__float_as_uint(pre_cuv.y) << 32) | __float_as_uint(pre_cuv.x);
+                pre_have = false;
+            }
+            return;
+        }
         if (starting) {
             if (pre_have) {   // a work item's first sample: made by refill
                 g.start(pre_k, kMedia);
@@ -659,6 +732,19 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
     };
     // seg: begin the segment here (else the caller does)
     auto camera_finish = [&](bool starting, float cu_, float cv_, V3 disk, bool seg = true) {
+        if constexpr (kRays) {   // the first segment is the record's ray: no lens, no time draw
+            if (starting) {
+                const float4 q0 = A.rays[(size_t)item * 3 + 0], q1 = A.rays[(size_t)item * 3 + 1];
+                r.o = mk(q0.x, q0.y, q0.z);
+                r.d = mk(q1.x, q1.y, q1.z);
+                r.time = q0.w;
+                beta = mk(1, 1, 1);
+                depth = 0;
+                if (kCount) cnt.samples++;
+                if (seg) begin_segment();
+            }
+            return;
+        }
         if (starting) {
             const CamView C = load_camera(lds_cam);
             V3 rd = scale(C.lens, disk);
@@ -745,7 +831,7 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
             const bool starting = phase == PH_IDLE && !finished && (!kBall || item != 0xFFFFFFFFu);
             float cu_ = (RT_SHADE_LEAN & 8) ? unset_f() : 0.f, cv_ = (RT_SHADE_LEAN & 8) ? unset_f() : 0.f;   // starting lanes only
             camera_begin(starting, cu_, cv_);
-            const V3 disk = coop_reject<2, kCount>(starting, g, slots, jt, lane, cnt, DiskCand());
+            const V3 disk = coop_reject<2, kCount>(!kRays && starting, g, slots, jt, lane, cnt, DiskCand());   // (kRays: no lens)
             camera_finish(starting, cu_, cv_, disk);
         }
         mark(0);
@@ -1035,7 +1121,8 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
         // material.h:41-47 for the scattering lanes, camera.h:6-12 for the new samples
         // (most of a ready batch asks: each lane tries its own first candidates, the rounds serve the rest)
         const uint64_t trips0 = cnt.w_rius, local0 = cnt.w_local;   // (kCount)
-        const V3 pt = coop_reject_mixed<kCount>(st.wants_sphere || starting, starting, g, slots, jt, lane, cnt,
+        const bool lens = !kRays && starting;   // (kRays: a new sample asks for no lens-disk point)
+        const V3 pt = coop_reject_mixed<kCount>(st.wants_sphere || lens, lens, g, slots, jt, lane, cnt,
                                                 A.coop_local, A.coop_local_min);
         if (kCount && lane == 0) {   // all 64 lanes are active here: lane 0 holds the wave-level trips
             const uint64_t local = cnt.w_local - local0, rounds = cnt.w_rius - trips0 - local;
@@ -1176,7 +1263,12 @@ __global__ __launch_bounds__((kMode & 3) == 1 ? RT_LDS_BLOCK : RT_BLOCK, RT_WAVE
 // build time).  It takes the megakernel and its launchers from here, holds no other kernel
 // and defines rt_launch_megakernel_fold.  (Not an RT_* knob: every library build compiles
 // both of its values.)
-#ifndef MEGAKERNEL_FOLD_UNIT
+// MEGAKERNEL_RAYS_UNIT (rt_kernel_rays.hip): likewise the unit of the ray-source variants
+// (kRays), which defines rt_launch_megakernel_rays.
+#if defined(MEGAKERNEL_FOLD_UNIT) || defined(MEGAKERNEL_RAYS_UNIT)
+#define MEGAKERNEL_SIDE_UNIT 1
+#endif
+#ifndef MEGAKERNEL_SIDE_UNIT
 // Adds one sample batch's partial sums to each pixel's running sum, in sample
 // order (main.cpp:311 `col += temp`, one add per sample with one sample per work
 // item), so the image does not depend on how the samples were split into batches
@@ -1232,7 +1324,7 @@ __global__ __launch_bounds__(256) void rt_math_probe_kernel(int fn, const float 
     }
     out[i] = r;
 }
-#endif  // MEGAKERNEL_FOLD_UNIT
+#endif  // MEGAKERNEL_SIDE_UNIT
 
 #ifdef RT_KNOB_CHECK
 // tests/test_device_knobs.py: a device-only build of final()'s variant (BVH2 in LDS, media)
@@ -1244,7 +1336,7 @@ template __global__ void rt_megakernel<false, false, 2, RT_FEAT_INST, 2>(RtKerne
 }  // namespace
 
 #ifndef RT_KNOB_CHECK
-#ifndef MEGAKERNEL_FOLD_UNIT
+#ifndef MEGAKERNEL_SIDE_UNIT
 extern "C" hipError_t rt_launch_math_probe(int fn, const float *a, const float *b, float *out, int n, hipStream_t stream) {
     hipLaunchKernelGGL(rt_math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fn, a, b, out, n);
     return hipGetLastError();
@@ -1252,9 +1344,9 @@ extern "C" hipError_t rt_launch_math_probe(int fn, const float *a, const float *
 #endif
 
 // --------------------------------------------------------------- launchers
-template <bool kCount, bool kProf, int kWidth, int kFeat, int kLds, bool kFold = false>
+template <bool kCount, bool kProf, int kWidth, int kFeat, int kLds, bool kFold = false, bool kRays = false>
 static hipError_t launch_one(const RtKernelArgs *a, int grid, hipStream_t stream) {
-    auto *k = rt_megakernel<kCount, kProf, kWidth, kFeat, kLds | (kFold ? 4 : 0)>;
+    auto *k = rt_megakernel<kCount, kProf, kWidth, kFeat, kLds | (kFold ? 4 : 0) | (kRays ? 8 : 0)>;
     size_t dyn = 0;
     if (kLds == 1) {
         // the variant's node layout (rt_megakernel's kSplit): dword planes need 56 KiB, float4 planes 64
@@ -1279,10 +1371,11 @@ static hipError_t launch_one(const RtKernelArgs *a, int grid, hipStream_t stream
             done.fetch_or(bit, std::memory_order_release);
         }
     }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kLds == 1 ? RT_LDS_BLOCK : RT_BLOCK), dyn, stream, *a);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(rt_mega_block(kLds | (kRays ? 8 : 0))), dyn, stream, *a);
     return hipGetLastError();
 }
 
+#ifndef MEGAKERNEL_RAYS_UNIT
 template <int kWidth, int kFeat, int kLds>
 static hipError_t launch_variant(const RtKernelArgs *a, int grid, int mode, hipStream_t stream) {
 #ifdef MEGAKERNEL_FOLD_UNIT
@@ -1325,11 +1418,54 @@ static hipError_t launch_features(const RtKernelArgs *a, int grid, int mode, hip
     }
 }
 
+#endif  // MEGAKERNEL_RAYS_UNIT
+
 // Compiled variants: every feature (any scene), media only (final(), and scenes with
 // no feature), instances (cornell_box), instances + media (cornell_smoke), checker +
 // pre-scan without media (the random scenes), each with the BVH2 in HBM or in LDS; the
 // wide BVHs (4, 8, compressed 8) run the all-feature variant from HBM.
-#ifdef MEGAKERNEL_FOLD_UNIT
+#if defined(MEGAKERNEL_RAYS_UNIT)
+// ... and, in their own unit, the ray-source variants: every feature, width 2, plain mode, one
+// per search mode
+extern "C" hipError_t rt_launch_megakernel_rays(const RtKernelArgs *a, int grid, hipStream_t stream) {
+    if (a->bvh_width != 2 || !a->rays || !a->radiance) return hipErrorInvalidValue;
+    if (a->scan) return launch_one<false, false, 2, RT_FEAT_ALL, 2, false, true>(a, grid, stream);
+    return a->lds_nodes ? launch_one<false, false, 2, RT_FEAT_ALL, 1, false, true>(a, grid, stream)
+                        : launch_one<false, false, 2, RT_FEAT_ALL, 0, false, true>(a, grid, stream);
+}
+extern "C" hipError_t rt_megakernel_rays_plan(int search, int stack_depth, int *blocks_per_cu, int *block_threads) {
+    search &= 3;
+    if (search == 3) return hipErrorInvalidValue;
+    *block_threads = rt_mega_block(search | 8);
+    // a property of the code objects, queried once per process (value + 1; 0: not yet): the LDS
+    // variant's static LDS bytes, the others' resident workgroups per CU
+    static std::atomic<int> known[3];
+    int v = known[search].load(std::memory_order_acquire) - 1;
+    if (v < 0) {
+        hipError_t e;
+        if (search == 1) {
+            hipFuncAttributes fa;
+            e = hipFuncGetAttributes(&fa, (const void *)rt_megakernel<false, false, 2, RT_FEAT_ALL, 1 | 8>);
+            v = (int)fa.sharedSizeBytes;
+        } else if (search == 2) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, rt_megakernel<false, false, 2, RT_FEAT_ALL, 2 | 8>, RT_BLOCK, 0);
+        } else {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, rt_megakernel<false, false, 2, RT_FEAT_ALL, 0 | 8>, RT_BLOCK, 0);
+        }
+        if (e != hipSuccess) return e;
+        known[search].store(v + 1, std::memory_order_release);
+    }
+    if (search == 1) {   // one workgroup per CU, if its LDS fits (what launch_one asks for)
+        const long need = (long)v + (long)lds_node_bytes<rt_lds_split(1, RT_FEAT_ALL, 2)>() + (long)RT_LDS_STACK_BYTES((long)stack_depth);
+        *blocks_per_cu = need <= RT_LDS_BUDGET ? 1 : 0;
+    } else {
+        *blocks_per_cu = v;
+    }
+    return hipSuccess;
+}
+// the unit announces its launchers to capi_radiance.cpp when it is linked in
+static const bool rays_unit_linked = (rt_rays_launch = RtRaysLaunch{rt_launch_megakernel_rays, rt_megakernel_rays_plan}, true);
+#elif defined(MEGAKERNEL_FOLD_UNIT)
 // ... and the right-fold variant of each width-2 one (plain mode only)
 extern "C" hipError_t rt_launch_megakernel_fold(const RtKernelArgs *a, int grid, hipStream_t stream) {
     if (a->bvh_width != 2) return hipErrorInvalidValue;
@@ -1419,5 +1555,5 @@ extern "C" int rt_megakernel_lds_static_bytes(void) {
     return (int)(4 * 64 + (RT_LDS_BLOCK / 64) * 64 * sizeof(CoopSlot) + RT_LDS_MEDIA * sizeof(MediumRec) + 6 * 16 + 16 +
                  (RT_LDS_BLOCK / 64) * RT_PRE * (8 + 8 + 8) + RT_LCG_JUMPS * 16 + 2 * 80 + 16 + 16 + 4) + 256;
 }
-#endif  // MEGAKERNEL_FOLD_UNIT
+#endif  // MEGAKERNEL_RAYS_UNIT / MEGAKERNEL_FOLD_UNIT
 #endif  // RT_KNOB_CHECK

@@ -135,6 +135,7 @@ int ensure_own_stream(rt_scene *s);   // created on first use (rt_scene_create)
 // capi_render.cpp
 void fill_scene_args(const rt_scene *s, RtKernelArgs &a);
 void fill_camera_args(const rt_camera_desc *cam, const rt_render_params *p, RtKernelArgs &a);
+void fill_sampler_args(RtKernelArgs &a);   // the shading stage's rejection sampler knobs (RTNW_COOP_LOCAL*)
 bool deep_first(const rt_scene *s);
 // rt_render_params' limits (rt_hip.h): RT_OK, or RT_ERR_INVALID with the message set
 int render_params_check(const rt_render_params *p);

@@ -294,6 +294,12 @@ void fill_camera_args(const rt_camera_desc *cam, const rt_render_params *p, RtKe
     a.seed = p->seed;
 }
 
+// The shading stage's rejection sampler (RT_COOP_LOCAL above): any setting computes the same.
+void fill_sampler_args(RtKernelArgs &a) {
+    a.coop_local = env_int("RTNW_COOP_LOCAL", RT_COOP_LOCAL, 0, 3);
+    a.coop_local_min = env_int("RTNW_COOP_LOCAL_MIN", RT_COOP_LOCAL_MIN, 1, 64);
+}
+
 // Whether a job lists the pixels whose primary rays enter a dense medium first
 // (RTNW_DEEP_FIRST=0: never).
 bool deep_first(const rt_scene *s) {
@@ -370,8 +376,7 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     a.ball_claim = env_int("RTNW_BALL_CLAIM", RT_BALL_CLAIM, 1, 64);
     a.ball_park = env_int("RTNW_BALL_PARK", 1, 0, 1);
     a.ball_drain = env_int("RTNW_BALL_DRAIN", 1, 0, 1);
-    a.coop_local = env_int("RTNW_COOP_LOCAL", RT_COOP_LOCAL, 0, 3);
-    a.coop_local_min = env_int("RTNW_COOP_LOCAL_MIN", RT_COOP_LOCAL_MIN, 1, 64);
+    fill_sampler_args(a);
     a.ns = p->spp;
     a.max_depth = p->max_depth;
     a.background = p->background;

@@ -175,6 +175,38 @@ def pack_rays(origin, dir, t_min=0.001, t_max=np.inf, time=0.0) -> np.ndarray:
     return rays
 
 
+class RtPathRay(ctypes.Structure):   # 48 bytes
+    _fields_ = [("origin", ctypes.c_float * 3), ("time", ctypes.c_float), ("dir", ctypes.c_float * 3),
+                ("skip", ctypes.c_uint32), ("pixel", ctypes.c_uint32), ("sample", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32 * 2)]
+
+
+class RtRadiance(ctypes.Structure):   # 16 bytes
+    _fields_ = [("rgb", ctypes.c_float * 3), ("status", ctypes.c_int32)]
+
+
+RT_RADIANCE_MAX_SKIP = 192
+# rt_path_ray and rt_radiance as numpy records (the ctypes structures' layout)
+PATH_RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("time", np.float32), ("dir", np.float32, 3), ("skip", np.uint32),
+                           ("pixel", np.uint32), ("sample", np.uint32), ("pad", np.uint32, 2)])
+RADIANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("status", np.int32)])
+
+
+def pack_path_rays(origin, dir, time=0.0, pixel=0, sample=0, skip=0) -> np.ndarray:
+    """rt_path_ray records ([n] PATH_RAY_DTYPE) from origins and directions [n, 3] (either may be
+    one vector for all) and time, pixel, sample and skip, scalars or [n]: the ray, the sample
+    stream's key numbers and the draws of that stream already spent (rt_hip.h)."""
+    o = np.asarray(origin, np.float32).reshape(-1, 3)
+    d = np.asarray(dir, np.float32).reshape(-1, 3)
+    n = max(len(o), len(d), *(np.size(x) for x in (time, pixel, sample, skip)))
+    rays = np.zeros(n, PATH_RAY_DTYPE)
+    rays["origin"], rays["dir"] = o, d
+    rays["time"] = np.asarray(time, np.float32).reshape(-1)
+    for name, x in (("pixel", pixel), ("sample", sample), ("skip", skip)):
+        rays[name] = np.asarray(x, np.uint32).reshape(-1)
+    return rays
+
+
 class RtCheckpoint(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("nx", ctypes.c_int32),
                 ("ny", ctypes.c_int32), ("samples_done", ctypes.c_uint32), ("max_depth", ctypes.c_int32),
@@ -245,6 +277,10 @@ def lib():
                                            P(ctypes.c_double)]),
             "rt_occluded_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                ctypes.c_void_p]),
+            "rt_radiance_rays": (ctypes.c_int, [ctypes.c_void_p, P(RtRenderParams), ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, P(ctypes.c_double)]),
+            "rt_radiance_rays_dev": (ctypes.c_int, [ctypes.c_void_p, P(RtRenderParams), ctypes.c_void_p, ctypes.c_int64,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
             "rt_device_alloc": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, P(ctypes.c_void_p)]),
             "rt_device_free": (ctypes.c_int, [ctypes.c_void_p]),
             "rt_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
@@ -277,12 +313,13 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass, the denoiser, the firefly clamp and the ray queries
+        # the feature pass, the denoiser, the firefly clamp, the ray queries and the radiance queries
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
                     "rt_copy_to_device",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
                     "rt_firefly", "rt_firefly_dev",
-                    "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev"}
+                    "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
+                    "rt_radiance_rays", "rt_radiance_rays_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -595,6 +632,25 @@ class Scene:
         """rt_occluded_dev: n rt_ray records in device memory into n bytes there."""
         _check(lib().rt_occluded_dev(self.handle, ctypes.c_void_p(rays_dev_ptr), n, ctypes.c_void_p(out_dev_ptr),
                                      ctypes.c_void_p(stream_ptr)))
+
+    def radiance_rays(self, params: RtRenderParams, rays, timing: bool = False):
+        """rt_radiance_rays: the path-traced radiance of each rt_path_ray record (pack_path_rays)
+        as [n] RADIANCE_DTYPE records (`rgb` [n, 3] float32, `status` 0 or RT_HIT_INVALID).  From
+        params: max_depth, t_min, background, seed.  timing: also the kernels' HIP-event ms."""
+        r = np.ascontiguousarray(rays)
+        if r.dtype != PATH_RAY_DTYPE:
+            raise TypeError("rays must be rt_path_ray records (PATH_RAY_DTYPE; see pack_path_rays)")
+        r = r.reshape(-1)
+        out = np.zeros(len(r), RADIANCE_DTYPE)
+        ms = ctypes.c_double(0.0)
+        _check(lib().rt_radiance_rays(self.handle, ctypes.byref(params), r.ctypes.data, len(r), out.ctypes.data,
+                                      ctypes.byref(ms)))
+        return (out, ms.value) if timing else out
+
+    def radiance_rays_dev(self, params: RtRenderParams, rays_dev_ptr: int, n: int, out_dev_ptr: int, stream_ptr: int = 0):
+        """rt_radiance_rays_dev: n rt_path_ray records in device memory into n rt_radiance records there."""
+        _check(lib().rt_radiance_rays_dev(self.handle, ctypes.byref(params), ctypes.c_void_p(rays_dev_ptr), n,
+                                          ctypes.c_void_p(out_dev_ptr), ctypes.c_void_p(stream_ptr)))
 
     def close(self):
         if self.handle:
