@@ -469,6 +469,76 @@ int rt_firefly_dev(int device, int nx, int ny, const float *color_dev, const flo
                    const float *moments_dev, const rt_firefly_params *fp, float *out_dev,
                    float *out_moments_dev, float *ratio_dev, void *stream);
 
+/* ------------------------------- reprojected frame history ahead of the denoiser */
+typedef struct rt_temporal_frame {   /* one struct for the frame, the history and the output */
+    const float   *color;    /* nx*ny*3, mean radiance */
+    const float   *guides;   /* nx*ny*8 as rt_render_features_dev packs them:
+                                albedo.rgb, coverage, normal.xyz, depth */
+    const float   *moments;  /* nx*ny*2 (sum y, sum y*y) or NULL */
+    const int32_t *len;      /* nx*ny samples those sums and that mean stand for;
+                                NULL in the current frame (every pixel: frame_spp) */
+} rt_temporal_frame;
+typedef struct rt_temporal_params {      /* 32 bytes */
+    int32_t max_history;   /* 0..2^23 samples of history a pixel may carry */
+    float cos_normal;      /* -1..1 */
+    float sigma_depth;     /* >= 0 */
+    int32_t frame_spp;     /* 1..65535: the samples behind every pixel of the current frame */
+    int32_t pad[4];        /* zero */
+} rt_temporal_params;
+/* Temporal accumulation (Schied et al. 2017, the step ahead of the filter): blends the current
+ * frame into the previous call's output, fetched where each pixel's surface point was seen by
+ * the previous camera.  One Jacobi pass (every value read is an input) over nx x ny pixels, row
+ * 0 on top.  `cur` is the frame (colour and moments as rt_render_tiles_moments writes them,
+ * guides as rt_render_features_dev does, len NULL), `hist` the previous call's `out` with the
+ * guides of that call's `cur`, or NULL for a first frame; `out` receives colour, moments (when
+ * given) and len — what rt_denoise reads as color, moments and spp.  out->guides is ignored and
+ * the pointers of `out` are written through: the caller keeps cur->guides as the next call's
+ * hist->guides.  With n_f = frame_spp:
+ *   No history (a first frame; or, below, W = 0, coverage != 1 under unequal cameras, n_h <= 0):
+ *     the output pixel is the frame's bit for bit, the moments the frame's, len = n_f.
+ *   Equal cameras (the two rt_camera_desc bytewise equal): a pixel's history is its own pixel
+ *     of `hist`, weight 1, no tests — the scene cannot change between calls, so nothing is
+ *     disoccluded; misses accumulate too.  n_h = min(hist len, max_history).
+ *   Otherwise a pixel (x, y) with coverage exactly 1 is reprojected: P = origin + dir *
+ *     (depth / |dir|), dir the camera's ray through the pixel centre and the lens centre,
+ *     s = (x + 0.5) / nx, t = ((ny - 1 - y) + 0.5) / ny.  With d = P - origin', P must lie in
+ *     front of the previous camera (d . w' < 0); d meets the plane of lower_left_corner',
+ *     horizontal', vertical' at (s', t'), read by projection on horizontal' and vertical';
+ *     fx = s' nx - 0.5, fy = (ny - 1) - (t' ny - 0.5), and the expected depth is z' = |d|.  Of the
+ *     four bilinear taps around (fx, fy) a tap q counts when its weight is positive, it is inside
+ *     the image, hist len[q] > 0, its coverage is exactly 1, n_p . n_q >= cos_normal and
+ *     |z' - z_q| <= sigma_depth * min(z', z_q) + 1e-6 (rt_firefly's depth test).  W is the sum of
+ *     the counting taps' weights; the history colour and per-sample moments mu = M / len are
+ *     their weight-normalised sums, n_h = min(min of their len, max_history).
+ *   Blend, n = n_h + n_f, a = float(n_f) / float(n): out = c_h + (c_f - c_h) * a, the same for
+ *     mu_1 and mu_2 against the frame's S / n_f; out moments = (mu_1 n, mu_2 n), out len = n: a
+ *     running mean until max_history, an exponential one after it, and an honest count.
+ * The exact float32 statement is tests/test_temporal_spec.py.  Inputs must be finite and depths
+ * non-negative.  Every call must be given a fresh sample range — sample_offset advanced by
+ * frame_spp from frame to frame: equal ranges at an equal camera repeat the same samples, and
+ * the accumulated count then claims samples that were never drawn.  Suggested: cos_normal 0.9,
+ * sigma_depth 0.1 (rt_firefly's), max_history 16 (DESIGN.md §7h records the sweep: beyond it
+ * the resampled history of a moving camera drifts faster than its noise falls).
+ * Host form: host pointers in all three frames; one staging allocation; *ms (when non-NULL)
+ * receives the kernel's time in ms.  Synchronous.
+ * RT_ERR_INVALID — all checked before the device is touched, the parameter named in
+ * rt_last_error() — for a null cur, cam, tp or out, a null cur->color, cur->guides, out->color
+ * or out->len, with a history a null prev_cam, hist->color, hist->guides or hist->len; nx or
+ * ny < 1 or nx * ny >= 2^31; a parameter outside the ranges above, NaN, or a nonzero pad;
+ * cur->moments and hist->moments not both given or both NULL, out->moments given without
+ * cur->moments; out->color equal to cur->color or hist->color, out->moments equal to
+ * hist->moments, out->len equal to hist->len (neighbours of the history are read: not in
+ * place; out->moments may be cur->moments). */
+int rt_temporal(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                const rt_temporal_frame *out, double *ms);
+/* The same with device pointers in the frames, enqueued on `stream`.  No workspace: calls may
+ * overlap.  Two history sets ping-pong: this call's `out` (with cur's guides) is the next
+ * call's `hist`, and the set before it the next `out`. */
+int rt_temporal_dev(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                    const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                    const rt_temporal_frame *out, void *stream);
+
 /* ------------------------------- ray queries on the caller's own rays */
 #define RT_HIT_MISS (-1)
 #define RT_HIT_INVALID (-2)

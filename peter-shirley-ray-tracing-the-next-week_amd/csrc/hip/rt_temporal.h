@@ -1,0 +1,29 @@
+// rt_temporal.h — launch interface of rt_temporal.hip: the reprojected frame history that runs
+// ahead of the denoiser (capi_temporal.cpp rt_temporal, rt_temporal_dev).
+// Internal to librt_hip.so.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_hip.h"
+
+// How a pixel finds its history: none (a first frame: the frame is copied), its own pixel (the
+// two cameras are bytewise equal), or the four taps around its reprojected surface point.
+enum { RT_TEMPORAL_FIRST = 0, RT_TEMPORAL_STATIC = 1, RT_TEMPORAL_REPROJECT = 2 };
+
+// One Jacobi pass over the nx x ny image.  The frames hold device pointers and have passed
+// capi_temporal.cpp's checks: cur (color, guides; moments or null), hist (color, guides, len;
+// moments as cur's; unread in mode RT_TEMPORAL_FIRST and may then be all null), out (color, len;
+// moments or null, only with cur's).  out's arrays are written; none of them is one of hist's,
+// and out->color is not cur->color.
+extern "C" hipError_t rt_launch_temporal(int nx, int ny, int mode, const rt_temporal_frame *cur,
+                                         const rt_camera_desc *cam, const rt_temporal_frame *hist,
+                                         const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                                         const rt_temporal_frame *out, hipStream_t stream);
+
+// capi_temporal.cpp reaches the launcher through this table, filled by rt_temporal.hip's static
+// initialiser when the unit is linked in (like rt_firefly.h's RtFireflyLaunch).
+struct RtTemporalLaunch {
+    decltype(&rt_launch_temporal) accumulate;
+};
+extern "C" RtTemporalLaunch rt_temporal_launch;   // defined (empty) in capi_temporal.cpp

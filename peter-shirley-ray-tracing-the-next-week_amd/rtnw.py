@@ -143,6 +143,20 @@ FIREFLY_DEFAULTS = dict(demodulate=1, radius=2, min_similar=3, k=8.0, floor=0.01
                         sigma_albedo=0.25)
 
 
+class RtTemporalFrame(ctypes.Structure):   # the frame, the history and the output of rt_temporal
+    _fields_ = [("color", ctypes.c_void_p), ("guides", ctypes.c_void_p), ("moments", ctypes.c_void_p),
+                ("len", ctypes.c_void_p)]
+
+
+class RtTemporalParams(ctypes.Structure):   # 32 bytes
+    _fields_ = [("max_history", ctypes.c_int32), ("cos_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+                ("frame_spp", ctypes.c_int32), ("pad", ctypes.c_int32 * 4)]
+
+
+# the frame history's suggested settings (DESIGN.md §7h records the sweep that chose max_history)
+TEMPORAL_DEFAULTS = dict(max_history=16, cos_normal=0.9, sigma_depth=0.1)
+
+
 class RtRay(ctypes.Structure):   # 48 bytes
     _fields_ = [("origin", ctypes.c_float * 3), ("t_min", ctypes.c_float), ("dir", ctypes.c_float * 3),
                 ("t_max", ctypes.c_float), ("time", ctypes.c_float), ("pad", ctypes.c_float * 3)]
@@ -269,6 +283,12 @@ def lib():
             "rt_firefly_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, P(RtFireflyParams), ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_temporal": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame), P(RtCameraDesc),
+                                           P(RtTemporalFrame), P(RtCameraDesc), P(RtTemporalParams), P(RtTemporalFrame),
+                                           P(ctypes.c_double)]),
+            "rt_temporal_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame), P(RtCameraDesc),
+                                               P(RtTemporalFrame), P(RtCameraDesc), P(RtTemporalParams),
+                                               P(RtTemporalFrame), ctypes.c_void_p]),
             "rt_trace_rays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                              P(ctypes.c_double)]),
             "rt_trace_rays_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -313,11 +333,12 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass, the denoiser, the firefly clamp, the ray queries and the radiance queries
+        # the feature pass, the denoiser, the firefly clamp, the frame history, the ray queries and the radiance
+        # queries
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
                     "rt_copy_to_device",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
-                    "rt_firefly", "rt_firefly_dev",
+                    "rt_firefly", "rt_firefly_dev", "rt_temporal", "rt_temporal_dev",
                     "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
                     "rt_radiance_rays", "rt_radiance_rays_dev"}
         for name, (res, args) in sig.items():
@@ -742,6 +763,70 @@ def firefly(color, features, moments=None, *, demodulate=None, radius=None, min_
                             ctypes.byref(ms)))
     res = [out] + ([om] if om is not None else []) + ([ratio] if want_ratio else []) + ([ms.value] if timing else [])
     return res[0] if len(res) == 1 else tuple(res)
+
+
+# -------------------------------------------------------------- frame history
+def temporal_params(frame_spp, max_history=None, cos_normal=None, sigma_depth=None):
+    given = dict(max_history=max_history, cos_normal=cos_normal, sigma_depth=sigma_depth)
+    v = {n: TEMPORAL_DEFAULTS[n] if x is None else x for n, x in given.items()}
+    return RtTemporalParams(max_history=int(v["max_history"]), cos_normal=v["cos_normal"], sigma_depth=v["sigma_depth"],
+                            frame_spp=int(frame_spp))
+
+
+def pack_guides(features) -> np.ndarray:
+    """The packed guides [ny, nx, 8] float32 (albedo.rgb, coverage, normal.xyz, depth:
+    rt_render_features_dev's layout) of Scene.render_features' dict; an array of that shape
+    passes through."""
+    if not isinstance(features, dict):
+        g = np.ascontiguousarray(features, np.float32)
+        if g.ndim != 3 or g.shape[-1] != 8:
+            raise ValueError("packed guides are [ny, nx, 8]")
+        return g
+    z = np.asarray(features["depth"], np.float32)
+    g = np.zeros(z.shape + (8,), np.float32)
+    g[..., 0:3] = np.asarray(features["albedo"], np.float32).reshape(z.shape + (3,))
+    g[..., 3] = np.asarray(features["coverage"], np.float32).reshape(z.shape)
+    g[..., 4:7] = np.asarray(features["normal"], np.float32).reshape(z.shape + (3,))
+    g[..., 7] = z
+    return g
+
+
+def temporal(color, features, moments, frame_spp, cam: Camera, history=None, prev_cam: Camera | None = None, *,
+             max_history=None, cos_normal=None, sigma_depth=None, device: int = 0, timing: bool = False):
+    """Temporal accumulation (rt_temporal) of the frame `color` [ny, nx, 3] of `frame_spp`
+    samples per pixel, rendered through `cam`, to run ahead of `denoise`: `features` is
+    Scene.render_features' dict (with its coverage) or the packed guides, `moments` [ny, nx, 2]
+    or None.  `history` is None for a first frame, else a dict of the previous call's results
+    and that frame's features: color, moments (None when this call has none), len and features,
+    seen through `prev_cam`.  Every frame must draw fresh samples (sample_offset advanced by
+    frame_spp).  Unset settings take TEMPORAL_DEFAULTS.  Returns (color, moments or None, len):
+    len [ny, nx] int32 is what `denoise` takes as its spp map (and the kernel's ms after them
+    with timing=True)."""
+    c = np.ascontiguousarray(color, np.float32)
+    ny, nx, _ = c.shape
+    g = pack_guides(features).reshape(ny, nx, 8)
+    m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
+    tp = temporal_params(frame_spp, max_history, cos_normal, sigma_depth)
+    out, om, ol = np.zeros_like(c), (None if m is None else np.zeros_like(m)), np.zeros((ny, nx), np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    cur = RtTemporalFrame(ptr(c), ptr(g), ptr(m), None)
+    dst = RtTemporalFrame(ptr(out), None, ptr(om), ptr(ol))
+    hist, keep = None, None
+    if history is not None:
+        if prev_cam is None:
+            raise ValueError("a history needs the camera it was rendered through (prev_cam)")
+        hm = history.get("moments")
+        keep = (np.ascontiguousarray(history["color"], np.float32).reshape(ny, nx, 3),
+                pack_guides(history["features"]).reshape(ny, nx, 8),
+                None if hm is None else np.ascontiguousarray(hm, np.float32).reshape(ny, nx, 2),
+                np.ascontiguousarray(history["len"], np.int32).reshape(ny, nx))
+        hist = RtTemporalFrame(*(ptr(a) for a in keep))
+    ms = ctypes.c_double(0.0)
+    _check(lib().rt_temporal(device, nx, ny, ctypes.byref(cur), ctypes.byref(cam.desc),
+                             None if hist is None else ctypes.byref(hist),
+                             None if prev_cam is None else ctypes.byref(prev_cam.desc), ctypes.byref(tp), ctypes.byref(dst),
+                             ctypes.byref(ms)))
+    return (out, om, ol, ms.value) if timing else (out, om, ol)
 
 
 # ------------------------------------------------------------ multi-GPU (RCCL)
