@@ -67,45 +67,14 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_features(const RtKernelArgs A, in
     // closest surface hit (hitable_list.h:20-32)
     float best_t = RT_FLT_MAX;
     int best_key = 0x7FFFFFFF;
-    uint32_t best_prim = 0xFFFFFFFFu;
-    auto test = [&](uint32_t q) {
-        int key, kind;
-        const float t = prim_t<true>(A.prims, A.insts, q, r, A.tmin, key, kind);
-        keep_closest(true, t, key, q, best_t, best_key, best_prim);
-    };
-    if (A.scan || !A.has_bvh) {   // a flat-scan scene: every primitive (at most RT_SCAN_MAX)
-        const uint32_t n = A.has_bvh ? A.nprims : 0u;
-        if (valid)
-            for (uint32_t q = 0; q < n; ++q) test(q);
-    } else {
-        if (valid)
-            for (uint32_t q = 0; q < (uint32_t)A.nprescan; ++q) test(q);   // kept out of the BVH (scene_lower.cpp)
-        const GlobalNodes gnodes{A.nodes};
-        const Slab sl = make_slab<0>(r, A.tmin);
-        Counters cnt;
-        uint32_t node = A.root;
-        int sp = 0;
-        bool trav = valid;
-        while (wballot(trav) != 0ull) {
-            if (trav) {
-                const uint32_t pleaf = descend<2, false, 1>(gnodes, node, sl, best_t, stk, sp, cnt);
-                if (pleaf != RT_EMPTY_CHILD) {
-                    const uint32_t first = RT_LEAF_FIRST(pleaf), nleaf = RT_LEAF_COUNT(pleaf);
-                    for (uint32_t q = 0; q < nleaf; ++q) test(first + q);
-                }
-                if (node == RT_EMPTY_CHILD) trav = false;   // the stack is empty too (descend pops)
-            }
-        }
-    }
+    uint32_t best_prim = RT_NO_PRIM;
+    lane_closest_hit<false>(A, r, A.tmin, valid, stk, best_t, best_key, best_prim);
 
-    const bool have = valid && best_prim != 0xFFFFFFFFu;
+    const bool have = valid && best_prim != RT_NO_PRIM;
     V3 alb = mk(1.0f, 1.0f, 1.0f), nrm = mk(0, 0, 0);
     float depth = 0.f, cov = 0.f;
     if (have) {
-        const Hit hr = prim_record<true, true>(A.prims, A.insts, A.mats, best_prim, r, best_t);
-        alb = material_colour(A, hr);
-        nrm = hr.n;
-        depth = best_t * len(r.d);
+        nrm = hit_guides(A, r, best_prim, best_t, alb, depth).n;
         cov = 1.0f;
     }
     if (valid) {

@@ -6,7 +6,8 @@
 //                     ray's own t_min and t_max — and the hit's record: the descriptor's
 //                     primitive and material indices, t, t * |d|, the world normal and the
 //                     material's colour, as the feature pass computes them.
-//   rt_trace<true>    the same search left at the lane's first accepted hit; no record.
+//   rt_trace<true>    the same search left at the lane's first accepted hit, in the kernel's own
+//                     body; no record.
 //
 // Constant media are ignored, as in the feature pass.  Compiled with -ffp-contract=off like
 // the megakernel.
@@ -15,20 +16,6 @@
 #include "rt_colour.h"
 
 namespace {
-
-#define RT_NO_PRIM 0xFFFFFFFFu
-
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// make_slab's planes for an axis the ray does not move along (or barely: a reciprocal that
-// overflows) are plane * inf - origin * inf: NaN, or an infinity whose sign says nothing about
-// whether the origin lies between the planes, and a box the ray runs through would be culled.
-// With -o/d = NaN both planes are NaN on that axis, which box_span's min / max ignore: the
-// axis culls nothing, and the primitive tests decide.
-__device__ __forceinline__ void slab_axis(const F2 &inv, F2 &no) {
-    const float q = finite_f(inv.x) && finite_f(no.x) ? no.x : __builtin_nanf("");
-    no = F2{q, q};
-}
 
 template <bool kAny>
 __global__ __launch_bounds__(RT_BLOCK) void rt_trace(const RtKernelArgs A, const float4 *__restrict__ rays, uint32_t n,
@@ -62,36 +49,43 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_trace(const RtKernelArgs A, const
     float best_t = q1.w >= RT_FLT_MAX ? RT_FLT_MAX : q1.w;   // +inf and FLT_MAX: the reference's MAXFLOAT
     int best_key = 0;
     uint32_t best_prim = RT_NO_PRIM;
-    auto test = [&](uint32_t q) {
-        int key, kind;
-        const float t = prim_t<true>(A.prims, A.insts, q, r, tmin, key, kind);
-        keep_closest(true, t, key, q, best_t, best_key, best_prim);
-    };
-    auto done = [&]() { return kAny && best_prim != RT_NO_PRIM; };   // occlusion: the first accepted hit ends the search
-    if (A.scan || !A.has_bvh) {   // a flat-scan scene: every primitive (at most RT_SCAN_MAX)
-        const uint32_t np = A.has_bvh ? A.nprims : 0u;
-        if (valid)
-            for (uint32_t q = 0; q < np && !done(); ++q) test(q);
+    if (!kAny) {
+        lane_closest_hit<true>(A, r, tmin, valid, stk, best_t, best_key, best_prim);
     } else {
-        if (valid)
-            for (uint32_t q = 0; q < (uint32_t)A.nprescan && !done(); ++q) test(q);   // kept out of the BVH (scene_lower.cpp)
-        const GlobalNodes gnodes{A.nodes};
-        Slab sl = make_slab<0>(r, tmin);
-        slab_axis(sl.ix, sl.nox);
-        slab_axis(sl.iy, sl.noy);
-        slab_axis(sl.iz, sl.noz);
-        Counters cnt;
-        uint32_t node = A.root;
-        int sp = 0;
-        bool trav = valid && !done();
-        while (wballot(trav) != 0ull) {
-            if (trav) {
-                const uint32_t pleaf = descend<2, false, 1>(gnodes, node, sl, best_t, stk, sp, cnt);
-                if (pleaf != RT_EMPTY_CHILD) {
-                    const uint32_t first = RT_LEAF_FIRST(pleaf), nleaf = RT_LEAF_COUNT(pleaf);
-                    for (uint32_t q = 0; q < nleaf && !done(); ++q) test(first + q);
+        // Occlusion keeps the search in its own body, left at the lane's first accepted hit: behind
+        // lane_closest_hit the scene's scalar argument loads no longer overlap the ray's loads, 0.2 us a
+        // call (profiles/r19/kernel_times.md).  A change to lane_closest_hit belongs here too.
+        auto test = [&](uint32_t q) {
+            int key, kind;
+            const float t = prim_t<true>(A.prims, A.insts, q, r, tmin, key, kind);
+            keep_closest(true, t, key, q, best_t, best_key, best_prim);
+        };
+        auto done = [&]() { return best_prim != RT_NO_PRIM; };
+        if (A.scan || !A.has_bvh) {   // a flat-scan scene: every primitive (at most RT_SCAN_MAX)
+            const uint32_t np = A.has_bvh ? A.nprims : 0u;
+            if (valid)
+                for (uint32_t q = 0; q < np && !done(); ++q) test(q);
+        } else {
+            if (valid)
+                for (uint32_t q = 0; q < (uint32_t)A.nprescan && !done(); ++q) test(q);   // kept out of the BVH (scene_lower.cpp)
+            const GlobalNodes gnodes{A.nodes};
+            Slab sl = make_slab<0>(r, tmin);
+            slab_axis(sl.ix, sl.nox);
+            slab_axis(sl.iy, sl.noy);
+            slab_axis(sl.iz, sl.noz);
+            Counters cnt;
+            uint32_t node = A.root;
+            int sp = 0;
+            bool trav = valid && !done();
+            while (wballot(trav) != 0ull) {
+                if (trav) {
+                    const uint32_t pleaf = descend<2, false, 1>(gnodes, node, sl, best_t, stk, sp, cnt);
+                    if (pleaf != RT_EMPTY_CHILD) {
+                        const uint32_t first = RT_LEAF_FIRST(pleaf), nleaf = RT_LEAF_COUNT(pleaf);
+                        for (uint32_t q = 0; q < nleaf && !done(); ++q) test(first + q);
+                    }
+                    if (node == RT_EMPTY_CHILD || done()) trav = false;   // the stack is empty too (descend pops)
                 }
-                if (node == RT_EMPTY_CHILD || done()) trav = false;   // the stack is empty too (descend pops)
             }
         }
     }
@@ -105,11 +99,9 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_trace(const RtKernelArgs A, const
     float t = 0.f, depth = 0.f;
     int prim = sane ? RT_HIT_MISS : RT_HIT_INVALID, mat = -1;
     if (have) {
-        const Hit hr = prim_record<true, true>(A.prims, A.insts, A.mats, best_prim, r, best_t);
-        alb = material_colour(A, hr);
+        const Hit hr = hit_guides(A, r, best_prim, best_t, alb, depth);
         nrm = hr.n;
         t = best_t;
-        depth = best_t * len(r.d);
         prim = fbits(A.prims[best_prim * 4 + 1].w);   // the descriptor's list index (scene_lower.cpp to_dprim)
         mat = hr.mat;
     }

@@ -1,5 +1,5 @@
 // capi_internal.h — what the units of the C ABI (capi_*.cpp) share: the scene object, the
-// error helpers, the grow-on-demand buffers and the launch-argument fillers.
+// error helpers, the grow-on-demand buffers, the launch-argument fillers and the side units' plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,10 @@ inline int hip_fail(hipError_t e, const char *what) {
     do {                                                \
         hipError_t e_ = (expr);                         \
         if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+    } while (0)
+#define RT_TRY(expr)                      \
+    do {                                  \
+        if (int rc_ = (expr)) return rc_; \
     } while (0)
 
 inline int env_int(const char *name, int dflt, int lo, int hi) {
@@ -145,5 +149,96 @@ struct JobSlots {
 };
 int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
                const JobSlots *js, float *out_dev, float *mom_dev, void *stream_v, rt_stats *stats);
+
+// The host form of a side unit (rt_denoise, rt_firefly, rt_temporal): one device buffer that
+// lives for the call, carved into regions of floats in the order they are declared (an int32
+// count takes a float's room), filled and read back by synchronous copies on the null stream,
+// and two events around the launches, which alone elapsed() reports.
+struct Staging {
+    DevBuf buf;
+    Events<2> ev;
+    rtnw::Regions plan;
+    rtnw::Region floats(size_t n) { return plan.add(n); }
+    int reserve() { return buf.reserve(plan.total * sizeof(float)); }   // once, after the last region
+    float *ptr(rtnw::Region r) const { return (float *)buf.p + r.at; }
+    float *ptr_if(const void *wanted, rtnw::Region r) const { return wanted ? ptr(r) : nullptr; }
+    int upload(rtnw::Region r, const void *src) {   // a null input is not there: skipped
+        if (src) HIP_TRY(hipMemcpy(ptr(r), src, r.n * sizeof(float), hipMemcpyHostToDevice));
+        return RT_OK;
+    }
+    int download(void *dst, rtnw::Region r) {   // a null output is not wanted: skipped
+        if (dst) HIP_TRY(hipMemcpy(dst, ptr(r), r.n * sizeof(float), hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
+    int begin() {
+        HIP_TRY(hipEventCreate(&ev[0]));
+        HIP_TRY(hipEventCreate(&ev[1]));
+        HIP_TRY(hipEventRecord(ev[0], nullptr));
+        return RT_OK;
+    }
+    int end() { HIP_TRY(hipEventRecord(ev[1], nullptr)); return RT_OK; }
+    int elapsed(double *ms) {   // after a download: the events have completed
+        float t = 0.f;
+        if (ms) HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        if (ms) *ms = (double)t;
+        return RT_OK;
+    }
+};
+
+// The argument checks the side units share, each at its place in its function's order; `f` is
+// the entry point's name.  RT_OK, or the error with the message set.
+inline int image_size_check(const std::string &f, int nx, int ny) {
+    if (nx < 1 || ny < 1 || (uint64_t)nx * (uint64_t)ny > 0x7FFFFFFFull)
+        return fail(RT_ERR_INVALID, f + ": nx and ny must be at least 1 (and nx * ny below 2^31)");
+    return RT_OK;
+}
+inline int ray_count_check(const std::string &f, int64_t n, bool *empty) {   // *empty: n == 0, nothing to do
+    *empty = n == 0;
+    if (!rtnw::ray_count_ok(n)) return fail(RT_ERR_INVALID, f + ": n must be in 0..2^31 - 1");
+    return RT_OK;
+}
+inline int scene_check(const std::string &f, const rt_scene *s) {
+    if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
+    if (s->bvh_width != 2) return fail(RT_ERR_UNSUPPORTED, f + " needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
+    return RT_OK;
+}
+inline int unit_missing(const std::string &f, const char *unit, const char *object) {
+    return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the " + unit + " unit (" + object + ")");
+}
+
+// The host form of a ray query: n records of in_bytes each through the scene's workspace
+// (a batch of records in, then its records out of out_bytes each), each batch copied in, launched
+// by launch(in_dev, m, out_dev, stream) and copied out on the scene's stream; *ms, when asked
+// for, is the launches' summed event time.  `knob` is the batch size's environment variable
+// (rtnw::plan_trace_batch).  A record out depends on its record in alone, so not on the batches.
+template <class Launch>
+int ray_batches(rt_scene *s, const void *in, size_t in_bytes, void *out, size_t out_bytes, int64_t n, const char *knob,
+                double *ms, Launch launch) {
+    HIP_TRY(hipSetDevice(s->device));
+    RT_TRY(ensure_own_stream(s));
+    const uint64_t per = rtnw::plan_trace_batch((uint64_t)n, std::getenv(knob));
+    RT_TRY(s->trace_ws.reserve((size_t)per * (in_bytes + out_bytes)));
+    char *in_dev = (char *)s->trace_ws.p, *out_dev = in_dev + (size_t)per * in_bytes;
+    Events<2> ev;
+    HIP_TRY(hipEventCreate(&ev[0]));
+    HIP_TRY(hipEventCreate(&ev[1]));
+    double total = 0.0;
+    for (uint64_t k0 = 0; k0 < (uint64_t)n; k0 += per) {
+        const uint64_t m = std::min<uint64_t>(per, (uint64_t)n - k0);
+        HIP_TRY(hipMemcpyAsync(in_dev, (const char *)in + (size_t)k0 * in_bytes, (size_t)m * in_bytes, hipMemcpyHostToDevice,
+                               s->own_stream));
+        HIP_TRY(hipEventRecord(ev[0], s->own_stream));
+        RT_TRY(launch(in_dev, (uint32_t)m, out_dev, s->own_stream));
+        HIP_TRY(hipEventRecord(ev[1], s->own_stream));
+        HIP_TRY(hipMemcpyAsync((char *)out + (size_t)k0 * out_bytes, out_dev, (size_t)m * out_bytes, hipMemcpyDeviceToHost,
+                               s->own_stream));
+        HIP_TRY(hipStreamSynchronize(s->own_stream));
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
+        total += (double)t;
+    }
+    if (ms) *ms = total;
+    return RT_OK;
+}
 
 #pragma GCC visibility pop

@@ -30,11 +30,8 @@ static int features_check(const char *fn, const rt_scene *s, const rt_camera_des
         return fail(RT_ERR_INVALID, f + ": RT_FLAG_COUNT, RT_FLAG_PROFILE, RT_FLAG_SUM_IN and RT_FLAG_SUM_OUT are not supported");
     if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > p->nx - w || y0 > p->ny - h)
         return fail(RT_ERR_INVALID, f + ": rectangle (x0, y0, w, h) empty or outside the image");
-    if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
-    if (s->bvh_width != 2)
-        return fail(RT_ERR_UNSUPPORTED, f + " needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
-    if (!rt_features_launch.sample)
-        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the features unit (rt_features.o)");
+    RT_TRY(scene_check(f, s));
+    if (!rt_features_launch.sample) return unit_missing(f, "features", "rt_features.o");
     if (s->has_moving && (cam->time0 < s->time0 || cam->time1 > s->time1))
         return fail(RT_ERR_INVALID, f + ": camera shutter outside the scene's time span (moving-sphere bounds)");
     return RT_OK;
@@ -73,8 +70,7 @@ static int features_run(rt_scene *s, const rt_camera_desc *cam, const rt_render_
 static int denoise_check(const char *fn, int nx, int ny, bool nulls, const rt_denoise_params *dp, bool moments, bool spp) {
     const std::string f(fn);
     if (nulls || !dp) return fail(RT_ERR_INVALID, f + ": null argument");
-    if (nx < 1 || ny < 1 || (uint64_t)nx * (uint64_t)ny > 0x7FFFFFFFull)
-        return fail(RT_ERR_INVALID, f + ": nx and ny must be at least 1 (and nx * ny below 2^31)");
+    RT_TRY(image_size_check(f, nx, ny));
     if (dp->iterations < 0 || dp->iterations > 8) return fail(RT_ERR_INVALID, f + ": iterations must be in 0..8");
     if (!(dp->sigma_color >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_color must not be negative or NaN");
     if (!(dp->sigma_depth >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_depth must not be negative or NaN");
@@ -82,8 +78,7 @@ static int denoise_check(const char *fn, int nx, int ny, bool nulls, const rt_de
         return fail(RT_ERR_INVALID, f + ": uniform_spp must be at least 1 when moments come without an spp map");
     if (dp->variance_filter != 0 && dp->variance_filter != 1)
         return fail(RT_ERR_INVALID, f + ": variance_filter must be 0 or 1");
-    if (!rt_denoise_launch.prepare)
-        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the denoise unit (rt_denoise.o)");
+    if (!rt_denoise_launch.prepare) return unit_missing(f, "denoise", "rt_denoise.o");
     return RT_OK;
 }
 
@@ -130,8 +125,7 @@ static int firefly_check(const char *fn, int nx, int ny, bool nulls, const rt_fi
                          bool out_moments, bool same) {
     const std::string f(fn);
     if (nulls || !fp) return fail(RT_ERR_INVALID, f + ": null argument");
-    if (nx < 1 || ny < 1 || (uint64_t)nx * (uint64_t)ny > 0x7FFFFFFFull)
-        return fail(RT_ERR_INVALID, f + ": nx and ny must be at least 1 (and nx * ny below 2^31)");
+    RT_TRY(image_size_check(f, nx, ny));
     if (fp->demodulate != 0 && fp->demodulate != 1) return fail(RT_ERR_INVALID, f + ": demodulate must be 0 or 1");
     if (fp->radius < 1 || fp->radius > 3) return fail(RT_ERR_INVALID, f + ": radius must be in 1..3");
     const int window = (2 * fp->radius + 1) * (2 * fp->radius + 1) - 1;
@@ -146,9 +140,29 @@ static int firefly_check(const char *fn, int nx, int ny, bool nulls, const rt_fi
     if (!(fp->sigma_albedo >= 0.0f)) return fail(RT_ERR_INVALID, f + ": sigma_albedo must not be negative or NaN");
     if (out_moments && !moments) return fail(RT_ERR_INVALID, f + ": out_moments needs moments");
     if (same) return fail(RT_ERR_INVALID, f + ": out must not be color (neighbours are read: not in place)");
-    if (!rt_firefly_launch.clamp)
-        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the firefly unit (rt_firefly.o)");
+    if (!rt_firefly_launch.clamp) return unit_missing(f, "firefly", "rt_firefly.o");
     return RT_OK;
+}
+
+// The packed guides of the host forms (8 floats per pixel: albedo.rgb, coverage, normal.xyz,
+// depth) from their planes, and back.  The filter and the clamp do not read the coverage: 0.
+static std::vector<float> pack_guides(size_t npix, const float *albedo, const float *normal, const float *depth) {
+    std::vector<float> g(npix * RT_GUIDE_FLOATS);
+    for (size_t q = 0; q < npix; q++) {
+        float *v = g.data() + q * RT_GUIDE_FLOATS;
+        v[0] = albedo[3 * q]; v[1] = albedo[3 * q + 1]; v[2] = albedo[3 * q + 2]; v[3] = 0.f;
+        v[4] = normal[3 * q]; v[5] = normal[3 * q + 1]; v[6] = normal[3 * q + 2]; v[7] = depth[q];
+    }
+    return g;
+}
+static void unpack_guides(const std::vector<float> &g, float *albedo, float *normal, float *depth, float *coverage) {
+    for (size_t q = 0; q < g.size() / RT_GUIDE_FLOATS; q++) {   // a null plane is not wanted
+        const float *v = g.data() + q * RT_GUIDE_FLOATS;
+        if (albedo) { albedo[3 * q] = v[0]; albedo[3 * q + 1] = v[1]; albedo[3 * q + 2] = v[2]; }
+        if (coverage) coverage[q] = v[3];
+        if (normal) { normal[3 * q] = v[4]; normal[3 * q + 1] = v[5]; normal[3 * q + 2] = v[6]; }
+        if (depth) depth[q] = v[7];
+    }
 }
 
 extern "C" {
@@ -162,8 +176,7 @@ int rt_render_features_dev(rt_scene *s, const rt_camera_desc *cam, const rt_rend
 
 int rt_render_features(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, int x0, int y0, int w, int h,
                        float *albedo, float *normal, float *depth, float *coverage) {
-    if (int rc = features_check("rt_render_features", s, cam, p, x0, y0, w, h, albedo || normal || depth || coverage))
-        return rc;
+    RT_TRY(features_check("rt_render_features", s, cam, p, x0, y0, w, h, albedo || normal || depth || coverage));
     HIP_TRY(hipSetDevice(s->device));
     const size_t npix = (size_t)w * h, bytes = npix * RT_GUIDE_FLOATS * sizeof(float);
     if (int rc = s->host_out.reserve(bytes)) return rc;
@@ -172,70 +185,45 @@ int rt_render_features(rt_scene *s, const rt_camera_desc *cam, const rt_render_p
     std::vector<float> g(npix * RT_GUIDE_FLOATS);
     HIP_TRY(hipMemcpyAsync(g.data(), s->host_out.p, bytes, hipMemcpyDeviceToHost, s->own_stream));
     HIP_TRY(hipStreamSynchronize(s->own_stream));
-    for (size_t q = 0; q < npix; q++) {
-        const float *v = g.data() + q * RT_GUIDE_FLOATS;
-        if (albedo) { albedo[3 * q] = v[0]; albedo[3 * q + 1] = v[1]; albedo[3 * q + 2] = v[2]; }
-        if (coverage) coverage[q] = v[3];
-        if (normal) { normal[3 * q] = v[4]; normal[3 * q + 1] = v[5]; normal[3 * q + 2] = v[6]; }
-        if (depth) depth[q] = v[7];
-    }
+    unpack_guides(g, albedo, normal, depth, coverage);
     return RT_OK;
 }
 
 int rt_denoise_dev(int device, int nx, int ny, const float *color_dev, const float *guides_dev, const float *moments_dev,
                    const int32_t *spp_dev, const rt_denoise_params *dp, float *out_dev, void *stream) {
-    if (int rc = denoise_check("rt_denoise_dev", nx, ny, !color_dev || !guides_dev || !out_dev, dp, moments_dev != nullptr,
-                               spp_dev != nullptr))
-        return rc;
+    RT_TRY(denoise_check("rt_denoise_dev", nx, ny, !color_dev || !guides_dev || !out_dev, dp, moments_dev != nullptr,
+                         spp_dev != nullptr));
     HIP_TRY(hipSetDevice(device));
     return denoise_run(device, nx, ny, color_dev, guides_dev, moments_dev, spp_dev, dp, out_dev, (hipStream_t)stream);
 }
 
 int rt_denoise(int device, int nx, int ny, const float *color, const float *albedo, const float *normal, const float *depth,
                const float *moments, const int32_t *spp, const rt_denoise_params *dp, float *out, double *ms) {
-    if (int rc = denoise_check("rt_denoise", nx, ny, !color || !albedo || !normal || !depth || !out, dp, moments != nullptr,
-                               spp != nullptr))
-        return rc;
+    RT_TRY(denoise_check("rt_denoise", nx, ny, !color || !albedo || !normal || !depth || !out, dp, moments != nullptr,
+                         spp != nullptr));
     HIP_TRY(hipSetDevice(device));
     const size_t npix = (size_t)nx * ny;
-    std::vector<float> g(npix * RT_GUIDE_FLOATS);
-    for (size_t q = 0; q < npix; q++) {   // the packed guides; coverage is not read by the filter
-        float *v = g.data() + q * RT_GUIDE_FLOATS;
-        v[0] = albedo[3 * q]; v[1] = albedo[3 * q + 1]; v[2] = albedo[3 * q + 2]; v[3] = 0.f;
-        v[4] = normal[3 * q]; v[5] = normal[3 * q + 1]; v[6] = normal[3 * q + 2]; v[7] = depth[q];
-    }
-    // one allocation: colour, guides, moments, spp, out
-    const size_t off_g = npix * 3, off_m = off_g + npix * RT_GUIDE_FLOATS, off_s = off_m + npix * 2, off_o = off_s + npix,
-                 total = off_o + npix * 3;
-    DevBuf staging;
-    Events<2> ev;
-    if (int rc = staging.reserve(total * sizeof(float))) return rc;
-    float *d = (float *)staging.p;
-    HIP_TRY(hipMemcpy(d, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d + off_g, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (moments) HIP_TRY(hipMemcpy(d + off_m, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
-    if (spp) HIP_TRY(hipMemcpy(d + off_s, spp, npix * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    HIP_TRY(hipEventRecord(ev[0], nullptr));
-    if (int rc = denoise_run(device, nx, ny, d, d + off_g, moments ? d + off_m : nullptr,
-                             spp ? (const int32_t *)(d + off_s) : nullptr, dp, d + off_o, nullptr))
-        return rc;
-    HIP_TRY(hipEventRecord(ev[1], nullptr));
-    HIP_TRY(hipMemcpy(out, d + off_o, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (ms) {
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-        *ms = (double)t;
-    }
-    return RT_OK;
+    const std::vector<float> g = pack_guides(npix, albedo, normal, depth);
+    Staging st;   // colour, guides, moments, spp, out
+    const auto r_c = st.floats(npix * 3), r_g = st.floats(g.size()), r_m = st.floats(npix * 2), r_s = st.floats(npix),
+               r_o = st.floats(npix * 3);
+    RT_TRY(st.reserve());
+    RT_TRY(st.upload(r_c, color));
+    RT_TRY(st.upload(r_g, g.data()));
+    RT_TRY(st.upload(r_m, moments));
+    RT_TRY(st.upload(r_s, spp));
+    RT_TRY(st.begin());
+    RT_TRY(denoise_run(device, nx, ny, st.ptr(r_c), st.ptr(r_g), st.ptr_if(moments, r_m), (const int32_t *)st.ptr_if(spp, r_s),
+                       dp, st.ptr(r_o), nullptr));
+    RT_TRY(st.end());
+    RT_TRY(st.download(out, r_o));
+    return st.elapsed(ms);
 }
 
 int rt_firefly_dev(int device, int nx, int ny, const float *color_dev, const float *guides_dev, const float *moments_dev,
                    const rt_firefly_params *fp, float *out_dev, float *out_moments_dev, float *ratio_dev, void *stream) {
-    if (int rc = firefly_check("rt_firefly_dev", nx, ny, !color_dev || !guides_dev || !out_dev, fp, moments_dev != nullptr,
-                               out_moments_dev != nullptr, out_dev == color_dev))
-        return rc;
+    RT_TRY(firefly_check("rt_firefly_dev", nx, ny, !color_dev || !guides_dev || !out_dev, fp, moments_dev != nullptr,
+                         out_moments_dev != nullptr, out_dev == color_dev));
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(rt_firefly_launch.clamp(nx, ny, color_dev, guides_dev, moments_dev, fp, out_dev, out_moments_dev, ratio_dev,
                                     (hipStream_t)stream));
@@ -244,42 +232,26 @@ int rt_firefly_dev(int device, int nx, int ny, const float *color_dev, const flo
 
 int rt_firefly(int device, int nx, int ny, const float *color, const float *albedo, const float *normal, const float *depth,
                const float *moments, const rt_firefly_params *fp, float *out, float *out_moments, float *ratio, double *ms) {
-    if (int rc = firefly_check("rt_firefly", nx, ny, !color || !albedo || !normal || !depth || !out, fp, moments != nullptr,
-                               out_moments != nullptr, out == color))
-        return rc;
+    RT_TRY(firefly_check("rt_firefly", nx, ny, !color || !albedo || !normal || !depth || !out, fp, moments != nullptr,
+                         out_moments != nullptr, out == color));
     HIP_TRY(hipSetDevice(device));
     const size_t npix = (size_t)nx * ny;
-    std::vector<float> g(npix * RT_GUIDE_FLOATS);
-    for (size_t q = 0; q < npix; q++) {   // the packed guides; coverage is not read by the clamp
-        float *v = g.data() + q * RT_GUIDE_FLOATS;
-        v[0] = albedo[3 * q]; v[1] = albedo[3 * q + 1]; v[2] = albedo[3 * q + 2]; v[3] = 0.f;
-        v[4] = normal[3 * q]; v[5] = normal[3 * q + 1]; v[6] = normal[3 * q + 2]; v[7] = depth[q];
-    }
-    // one allocation: guides, colour, moments, out, out moments, ratio (the guides first: 16-B loads)
-    const size_t off_c = npix * RT_GUIDE_FLOATS, off_m = off_c + npix * 3, off_o = off_m + npix * 2, off_om = off_o + npix * 3,
-                 off_r = off_om + npix * 2, total = off_r + npix;
-    DevBuf staging;
-    Events<2> ev;
-    if (int rc = staging.reserve(total * sizeof(float))) return rc;
-    float *d = (float *)staging.p;
-    HIP_TRY(hipMemcpy(d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d + off_c, color, npix * 3 * sizeof(float), hipMemcpyHostToDevice));
-    if (moments) HIP_TRY(hipMemcpy(d + off_m, moments, npix * 2 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    HIP_TRY(hipEventRecord(ev[0], nullptr));
-    HIP_TRY(rt_firefly_launch.clamp(nx, ny, d + off_c, d, moments ? d + off_m : nullptr, fp, d + off_o,
-                                    out_moments ? d + off_om : nullptr, ratio ? d + off_r : nullptr, nullptr));
-    HIP_TRY(hipEventRecord(ev[1], nullptr));
-    HIP_TRY(hipMemcpy(out, d + off_o, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_moments) HIP_TRY(hipMemcpy(out_moments, d + off_om, npix * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (ratio) HIP_TRY(hipMemcpy(ratio, d + off_r, npix * sizeof(float), hipMemcpyDeviceToHost));
-    if (ms) {
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-        *ms = (double)t;
-    }
-    return RT_OK;
+    const std::vector<float> g = pack_guides(npix, albedo, normal, depth);
+    Staging st;   // guides, colour, moments, out, out moments, ratio (the guides first: 16-B loads)
+    const auto r_g = st.floats(g.size()), r_c = st.floats(npix * 3), r_m = st.floats(npix * 2), r_o = st.floats(npix * 3),
+               r_om = st.floats(npix * 2), r_r = st.floats(npix);
+    RT_TRY(st.reserve());
+    RT_TRY(st.upload(r_g, g.data()));
+    RT_TRY(st.upload(r_c, color));
+    RT_TRY(st.upload(r_m, moments));
+    RT_TRY(st.begin());
+    HIP_TRY(rt_firefly_launch.clamp(nx, ny, st.ptr(r_c), st.ptr(r_g), st.ptr_if(moments, r_m), fp, st.ptr(r_o),
+                                    st.ptr_if(out_moments, r_om), st.ptr_if(ratio, r_r), nullptr));
+    RT_TRY(st.end());
+    RT_TRY(st.download(out, r_o));
+    RT_TRY(st.download(out_moments, r_om));
+    RT_TRY(st.download(ratio, r_r));
+    return st.elapsed(ms);
 }
 
 }  // extern "C"

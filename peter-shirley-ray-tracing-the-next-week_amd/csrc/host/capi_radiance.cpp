@@ -1,6 +1,6 @@
 // capi_radiance.cpp — radiance queries on caller-supplied rays (rt_hip.h rt_radiance_rays and
-// its _dev form; rt_kernel.hip kRays, rt_kernel_rays.hip): the argument checks,
-// the host form's batches and the launch of the megakernel's ray-source variant.
+// its _dev form; rt_kernel.hip kRays, rt_kernel_rays.hip): the argument checks
+// and the launch of the megakernel's ray-source variant.
 #include <cmath>
 
 #include "capi_internal.h"
@@ -18,12 +18,8 @@ static_assert(sizeof(rt_path_ray) == RT_PATH_RAY_BYTES && sizeof(rt_radiance) ==
 static int radiance_check(const char *fn, const rt_scene *s, const rt_render_params *p, const void *rays, int64_t n,
                           const void *out, bool *empty) {
     const std::string f(fn);
-    *empty = false;
-    if (!rtnw::ray_count_ok(n)) return fail(RT_ERR_INVALID, f + ": n must be in 0..2^31 - 1");
-    if (n == 0) {
-        *empty = true;
-        return RT_OK;
-    }
+    RT_TRY(ray_count_check(f, n, empty));
+    if (*empty) return RT_OK;
     if (!p) return fail(RT_ERR_INVALID, f + ": null parameters");
     if (!rays) return fail(RT_ERR_INVALID, f + ": null rays");
     if (!out) return fail(RT_ERR_INVALID, f + ": null output");
@@ -31,10 +27,8 @@ static int radiance_check(const char *fn, const rt_scene *s, const rt_render_par
     if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID, f + ": t_min is not finite");
     if (p->background != RT_BG_BLACK && p->background != RT_BG_SKY) return fail(RT_ERR_INVALID, f + ": background outside RT_BG_*");
     if (p->flags != 0) return fail(RT_ERR_INVALID, f + ": no flag applies (there are no right-fold, counting or profiling forms)");
-    if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
-    if (s->bvh_width != 2) return fail(RT_ERR_UNSUPPORTED, f + " needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
-    if (!rt_rays_launch.launch)
-        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the rays unit (rt_kernel_rays.o)");
+    RT_TRY(scene_check(f, s));
+    if (!rt_rays_launch.launch) return unit_missing(f, "rays", "rt_kernel_rays.o");
     return RT_OK;
 }
 
@@ -91,31 +85,10 @@ int rt_radiance_rays(rt_scene *s, const rt_render_params *p, const rt_path_ray *
     bool empty;
     if (int rc = radiance_check("rt_radiance_rays", s, p, rays, n, out, &empty)) return rc;
     if (empty) return RT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (int rc = ensure_own_stream(s)) return rc;
-    // batches of rays through the scene's workspace (rays, then records), each copied in, traced
-    // and copied out on the scene's stream; a ray's record depends on that ray alone
-    const uint64_t per = rtnw::plan_trace_batch((uint64_t)n, std::getenv("RTNW_RADIANCE_BATCH"));
-    if (int rc = s->trace_ws.reserve((size_t)per * (RT_PATH_RAY_BYTES + RT_RADIANCE_BYTES))) return rc;
-    char *rays_dev = (char *)s->trace_ws.p, *out_dev = rays_dev + (size_t)per * RT_PATH_RAY_BYTES;
-    Events<2> ev;
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    double total = 0.0;
-    for (uint64_t k0 = 0; k0 < (uint64_t)n; k0 += per) {
-        const uint64_t m = std::min<uint64_t>(per, (uint64_t)n - k0);
-        HIP_TRY(hipMemcpyAsync(rays_dev, rays + k0, (size_t)m * RT_PATH_RAY_BYTES, hipMemcpyHostToDevice, s->own_stream));
-        HIP_TRY(hipEventRecord(ev[0], s->own_stream));
-        if (int rc = radiance_launch(s, p, rays_dev, (uint32_t)m, out_dev, s->own_stream)) return rc;
-        HIP_TRY(hipEventRecord(ev[1], s->own_stream));
-        HIP_TRY(hipMemcpyAsync(out + k0, out_dev, (size_t)m * RT_RADIANCE_BYTES, hipMemcpyDeviceToHost, s->own_stream));
-        HIP_TRY(hipStreamSynchronize(s->own_stream));
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-        total += (double)t;
-    }
-    if (ms) *ms = total;
-    return RT_OK;
+    return ray_batches(s, rays, RT_PATH_RAY_BYTES, out, RT_RADIANCE_BYTES, n, "RTNW_RADIANCE_BATCH", ms,
+                       [&](const void *rays_dev, uint32_t m, void *out_dev, hipStream_t stream) {
+                           return radiance_launch(s, p, rays_dev, m, out_dev, stream);
+                       });
 }
 
 int rt_radiance_rays_dev(rt_scene *s, const rt_render_params *p, const rt_path_ray *rays_dev, int64_t n, rt_radiance *out_dev,

@@ -29,8 +29,7 @@ static int temporal_check(const char *fn, int nx, int ny, const rt_temporal_fram
         if (!hist->guides) return fail(RT_ERR_INVALID, f + ": null argument (hist->guides)");
         if (!hist->len) return fail(RT_ERR_INVALID, f + ": null argument (hist->len)");
     }
-    if (nx < 1 || ny < 1 || (uint64_t)nx * (uint64_t)ny > 0x7FFFFFFFull)
-        return fail(RT_ERR_INVALID, f + ": nx and ny must be at least 1 (and nx * ny below 2^31)");
+    RT_TRY(image_size_check(f, nx, ny));
     if (tp->max_history < 0 || tp->max_history > (1 << 23))
         return fail(RT_ERR_INVALID, f + ": max_history must be in 0..2^23");
     if (!(tp->cos_normal >= -1.0f && tp->cos_normal <= 1.0f)) return fail(RT_ERR_INVALID, f + ": cos_normal must be in -1..1");
@@ -48,8 +47,7 @@ static int temporal_check(const char *fn, int nx, int ny, const rt_temporal_fram
         return fail(RT_ERR_INVALID, f + ": out->moments must not be hist->moments (neighbours are read: not in place)");
     if (hist && out->len == hist->len)
         return fail(RT_ERR_INVALID, f + ": out->len must not be hist->len (neighbours are read: not in place)");
-    if (!rt_temporal_launch.accumulate)
-        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the temporal unit (rt_temporal.o)");
+    if (!rt_temporal_launch.accumulate) return unit_missing(f, "temporal", "rt_temporal.o");
     return RT_OK;
 }
 
@@ -77,44 +75,34 @@ int rt_temporal(int device, int nx, int ny, const rt_temporal_frame *cur, const 
     if (int rc = temporal_check("rt_temporal", nx, ny, cur, cam, hist, prev_cam, tp, out)) return rc;
     HIP_TRY(hipSetDevice(device));
     const size_t npix = (size_t)nx * ny;
-    const bool mom = cur->moments != nullptr, out_mom = out->moments != nullptr;
-    // one allocation, in floats (an int32 count takes a float's room); the guides first: 16-B loads
+    // in floats (an int32 count takes a float's room); the guides first: 16-B loads
     const size_t g = npix * RT_GUIDE_FLOATS, c = npix * 3, m = npix * 2, l = npix;
-    const size_t off_cg = 0, off_hg = off_cg + g, off_cc = off_hg + g, off_hc = off_cc + c, off_oc = off_hc + c,
-                 off_cm = off_oc + c, off_hm = off_cm + m, off_om = off_hm + m, off_hl = off_om + m, off_ol = off_hl + l,
-                 total = off_ol + l;
-    DevBuf staging;
-    Events<2> ev;
-    if (int rc = staging.reserve(total * sizeof(float))) return rc;
-    float *d = (float *)staging.p;
-    HIP_TRY(hipMemcpy(d + off_cg, cur->guides, g * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d + off_cc, cur->color, c * sizeof(float), hipMemcpyHostToDevice));
-    if (mom) HIP_TRY(hipMemcpy(d + off_cm, cur->moments, m * sizeof(float), hipMemcpyHostToDevice));
+    Staging st;
+    const auto cur_g = st.floats(g), hist_g = st.floats(g), cur_c = st.floats(c), hist_c = st.floats(c), out_c = st.floats(c),
+               cur_m = st.floats(m), hist_m = st.floats(m), out_m = st.floats(m), hist_l = st.floats(l), out_l = st.floats(l);
+    RT_TRY(st.reserve());
+    RT_TRY(st.upload(cur_g, cur->guides));
+    RT_TRY(st.upload(cur_c, cur->color));
+    RT_TRY(st.upload(cur_m, cur->moments));
     if (hist) {
-        HIP_TRY(hipMemcpy(d + off_hg, hist->guides, g * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d + off_hc, hist->color, c * sizeof(float), hipMemcpyHostToDevice));
-        if (mom) HIP_TRY(hipMemcpy(d + off_hm, hist->moments, m * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d + off_hl, hist->len, l * sizeof(int32_t), hipMemcpyHostToDevice));
+        RT_TRY(st.upload(hist_g, hist->guides));
+        RT_TRY(st.upload(hist_c, hist->color));
+        RT_TRY(st.upload(hist_m, cur->moments ? hist->moments : nullptr));
+        RT_TRY(st.upload(hist_l, hist->len));
     }
-    const rt_temporal_frame dcur = {d + off_cc, d + off_cg, mom ? d + off_cm : nullptr, nullptr};
-    const rt_temporal_frame dhist = {d + off_hc, d + off_hg, mom ? d + off_hm : nullptr, (const int32_t *)(d + off_hl)};
-    const rt_temporal_frame dout = {d + off_oc, nullptr, out_mom ? d + off_om : nullptr, (const int32_t *)(d + off_ol)};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    HIP_TRY(hipEventRecord(ev[0], nullptr));
+    const rt_temporal_frame dcur = {st.ptr(cur_c), st.ptr(cur_g), st.ptr_if(cur->moments, cur_m), nullptr};
+    const rt_temporal_frame dhist = {st.ptr(hist_c), st.ptr(hist_g), st.ptr_if(cur->moments, hist_m),
+                                     (const int32_t *)st.ptr(hist_l)};
+    const rt_temporal_frame dout = {st.ptr(out_c), nullptr, st.ptr_if(out->moments, out_m), (const int32_t *)st.ptr(out_l)};
+    RT_TRY(st.begin());
     HIP_TRY(rt_temporal_launch.accumulate(nx, ny, temporal_mode(hist, cam, prev_cam), &dcur, cam, hist ? &dhist : nullptr,
                                           prev_cam, tp, &dout, nullptr));
-    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    RT_TRY(st.end());
     // the output frame's pointers are written through (rt_hip.h)
-    HIP_TRY(hipMemcpy((float *)out->color, d + off_oc, c * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_mom) HIP_TRY(hipMemcpy((float *)out->moments, d + off_om, m * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy((int32_t *)out->len, d + off_ol, l * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (ms) {
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-        *ms = (double)t;
-    }
-    return RT_OK;
+    RT_TRY(st.download((float *)out->color, out_c));
+    RT_TRY(st.download((float *)out->moments, out_m));
+    RT_TRY(st.download((int32_t *)out->len, out_l));
+    return st.elapsed(ms);
 }
 
 }  // extern "C"

@@ -12,18 +12,12 @@ static_assert(sizeof(rt_ray) == RT_RAY_BYTES && sizeof(rt_hit) == RT_HIT_BYTES, 
 // RT_OK with *empty set: n == 0, nothing to do (whatever the other arguments are).
 static int trace_check(const char *fn, const rt_scene *s, const void *rays, int64_t n, const void *out, bool *empty) {
     const std::string f(fn);
-    *empty = false;
-    if (!rtnw::ray_count_ok(n)) return fail(RT_ERR_INVALID, f + ": n must be in 0..2^31 - 1");
-    if (n == 0) {
-        *empty = true;
-        return RT_OK;
-    }
+    RT_TRY(ray_count_check(f, n, empty));
+    if (*empty) return RT_OK;
     if (!rays) return fail(RT_ERR_INVALID, f + ": null rays");
     if (!out) return fail(RT_ERR_INVALID, f + ": null output");
-    if (!s) return fail(RT_ERR_INVALID, f + ": null scene");
-    if (s->bvh_width != 2) return fail(RT_ERR_UNSUPPORTED, f + " needs a scene with a 2-wide BVH (RTNW_BVH_WIDTH=2)");
-    if (!rt_trace_launch.trace)
-        return fail(RT_ERR_UNSUPPORTED, f + ": this library was linked without the trace unit (rt_trace.o)");
+    RT_TRY(scene_check(f, s));
+    if (!rt_trace_launch.trace) return unit_missing(f, "trace", "rt_trace.o");
     return RT_OK;
 }
 
@@ -35,35 +29,12 @@ static int trace_launch(const rt_scene *s, const void *rays_dev, uint32_t n, boo
     return RT_OK;
 }
 
-// The host forms: batches of rays through the scene's workspace (rays, then results), each
-// copied in, traced and copied out on the scene's stream.  A ray's result depends on that ray
-// alone, so not on the batches.
+// The host forms: batches of rays through the scene's workspace (ray_batches).
 static int trace_host(rt_scene *s, const rt_ray *rays, int64_t n, bool any, void *out, double *ms) {
-    HIP_TRY(hipSetDevice(s->device));
-    if (int rc = ensure_own_stream(s)) return rc;
-    const size_t out_bytes = any ? 1 : RT_HIT_BYTES;
-    const uint64_t per = rtnw::plan_trace_batch((uint64_t)n, std::getenv("RTNW_TRACE_BATCH"));
-    if (int rc = s->trace_ws.reserve((size_t)per * (RT_RAY_BYTES + out_bytes))) return rc;
-    char *rays_dev = (char *)s->trace_ws.p, *out_dev = rays_dev + (size_t)per * RT_RAY_BYTES;
-    Events<2> ev;
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    double total = 0.0;
-    for (uint64_t k0 = 0; k0 < (uint64_t)n; k0 += per) {
-        const uint64_t m = std::min<uint64_t>(per, (uint64_t)n - k0);
-        HIP_TRY(hipMemcpyAsync(rays_dev, rays + k0, (size_t)m * RT_RAY_BYTES, hipMemcpyHostToDevice, s->own_stream));
-        HIP_TRY(hipEventRecord(ev[0], s->own_stream));
-        if (int rc = trace_launch(s, rays_dev, (uint32_t)m, any, out_dev, s->own_stream)) return rc;
-        HIP_TRY(hipEventRecord(ev[1], s->own_stream));
-        HIP_TRY(hipMemcpyAsync((char *)out + (size_t)k0 * out_bytes, out_dev, (size_t)m * out_bytes, hipMemcpyDeviceToHost,
-                               s->own_stream));
-        HIP_TRY(hipStreamSynchronize(s->own_stream));
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
-        total += (double)t;
-    }
-    if (ms) *ms = total;
-    return RT_OK;
+    return ray_batches(s, rays, RT_RAY_BYTES, out, any ? 1 : RT_HIT_BYTES, n, "RTNW_TRACE_BATCH", ms,
+                       [&](const void *rays_dev, uint32_t m, void *out_dev, hipStream_t stream) {
+                           return trace_launch(s, rays_dev, m, any, out_dev, stream);
+                       });
 }
 
 extern "C" {

@@ -72,5 +72,15 @@ int plan_feature_batches(uint64_t npix, int spp, uint64_t pixel_bytes, uint64_t 
 inline bool ray_count_ok(int64_t n) { return n >= 0 && n <= 0x7FFFFFFFll; }
 uint64_t plan_trace_batch(uint64_t n, const char *knob);
 
+// One buffer carved into regions declared one after another (capi_internal.h Staging): add(n)
+// is the next region, n elements from where the one before ended; total is what all of them take.
+struct Region {
+    size_t at, n;
+};
+struct Regions {
+    size_t total = 0;
+    Region add(size_t n) { total += n; return Region{total - n, n}; }
+};
+
 }  // namespace rtnw
 #pragma GCC visibility pop

@@ -370,6 +370,25 @@ def _check(rc):
     return rc
 
 
+def _ptr(a):
+    """An optional array's address: None stays None (a null pointer)."""
+    return None if a is None else a.ctypes.data
+
+
+def _params(T, defaults, ints, given, **fixed):
+    """The ctypes params struct T: the `given` settings, None taking its value in `defaults` and
+    those named in `ints` cast with int(), beside the `fixed` fields, which have no default."""
+    v = {n: defaults[n] if x is None else x for n, x in given.items()}
+    return T(**{n: int(x) if n in ints else x for n, x in v.items()}, **fixed)
+
+
+def _planes(features, ny, nx):
+    """The albedo, normal and depth planes of a features dict (Scene.render_features')."""
+    return (np.ascontiguousarray(features["albedo"], np.float32).reshape(ny, nx, 3),
+            np.ascontiguousarray(features["normal"], np.float32).reshape(ny, nx, 3),
+            np.ascontiguousarray(features["depth"], np.float32).reshape(ny, nx))
+
+
 def header_symbols(path: str = HEADER):
     """Function names declared in include/rt_hip.h."""
     text = open(path).read()
@@ -688,12 +707,9 @@ class Scene:
 # ------------------------------------------------------------------- denoiser
 def denoise_params(iterations=None, demodulate=None, sigma_color=None, sigma_depth=None, uniform_spp=0,
                    variance_filter=0):
-    d = DENOISE_DEFAULTS
-    return RtDenoiseParams(iterations=d["iterations"] if iterations is None else iterations,
-                           demodulate=d["demodulate"] if demodulate is None else int(demodulate),
-                           sigma_color=d["sigma_color"] if sigma_color is None else sigma_color,
-                           sigma_depth=d["sigma_depth"] if sigma_depth is None else sigma_depth,
-                           uniform_spp=uniform_spp, variance_filter=int(variance_filter))
+    given = dict(iterations=iterations, demodulate=demodulate, sigma_color=sigma_color, sigma_depth=sigma_depth)
+    return _params(RtDenoiseParams, DENOISE_DEFAULTS, ("demodulate",), given, uniform_spp=uniform_spp,
+                   variance_filter=int(variance_filter))
 
 
 def denoise(color, features, moments=None, spp=None, *, iterations=None, demodulate=None, sigma_color=None,
@@ -706,9 +722,7 @@ def denoise(color, features, moments=None, spp=None, *, iterations=None, demodul
     Unset settings take DENOISE_DEFAULTS.  Returns the filtered image (and the kernels' ms with timing=True)."""
     c = np.ascontiguousarray(color, np.float32)
     ny, nx, _ = c.shape
-    a = np.ascontiguousarray(features["albedo"], np.float32).reshape(ny, nx, 3)
-    n = np.ascontiguousarray(features["normal"], np.float32).reshape(ny, nx, 3)
-    z = np.ascontiguousarray(features["depth"], np.float32).reshape(ny, nx)
+    a, n, z = _planes(features, ny, nx)
     m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
     smap, uniform = None, 0
     if spp is not None and np.ndim(spp) == 0:
@@ -719,8 +733,7 @@ def denoise(color, features, moments=None, spp=None, *, iterations=None, demodul
     out = np.zeros_like(c)
     ms = ctypes.c_double(0.0)
     _check(lib().rt_denoise(device, nx, ny, c.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,
-                            None if m is None else m.ctypes.data, None if smap is None else smap.ctypes.data,
-                            ctypes.byref(dp), out.ctypes.data, ctypes.byref(ms)))
+                            _ptr(m), _ptr(smap), ctypes.byref(dp), out.ctypes.data, ctypes.byref(ms)))
     return (out, ms.value) if timing else out
 
 
@@ -729,10 +742,7 @@ def firefly_params(demodulate=None, radius=None, min_similar=None, k=None, floor
                    sigma_depth=None, sigma_albedo=None):
     given = dict(demodulate=demodulate, radius=radius, min_similar=min_similar, k=k, floor=floor,
                  cos_normal=cos_normal, sigma_depth=sigma_depth, sigma_albedo=sigma_albedo)
-    v = {n: FIREFLY_DEFAULTS[n] if x is None else x for n, x in given.items()}
-    return RtFireflyParams(demodulate=int(v["demodulate"]), radius=int(v["radius"]), min_similar=int(v["min_similar"]),
-                           k=v["k"], floor=v["floor"], cos_normal=v["cos_normal"], sigma_depth=v["sigma_depth"],
-                           sigma_albedo=v["sigma_albedo"])
+    return _params(RtFireflyParams, FIREFLY_DEFAULTS, ("demodulate", "radius", "min_similar"), given)
 
 
 def firefly(color, features, moments=None, *, demodulate=None, radius=None, min_similar=None, k=None, floor=None,
@@ -748,9 +758,7 @@ def firefly(color, features, moments=None, *, demodulate=None, radius=None, min_
     timing=True (a tuple when more than the image)."""
     c = np.ascontiguousarray(color, np.float32)
     ny, nx, _ = c.shape
-    a = np.ascontiguousarray(features["albedo"], np.float32).reshape(ny, nx, 3)
-    n = np.ascontiguousarray(features["normal"], np.float32).reshape(ny, nx, 3)
-    z = np.ascontiguousarray(features["depth"], np.float32).reshape(ny, nx)
+    a, n, z = _planes(features, ny, nx)
     m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
     fp = firefly_params(demodulate, radius, min_similar, k, floor, cos_normal, sigma_depth, sigma_albedo)
     out = np.zeros_like(c)
@@ -758,9 +766,7 @@ def firefly(color, features, moments=None, *, demodulate=None, radius=None, min_
     ratio = np.zeros((ny, nx), np.float32) if want_ratio else None
     ms = ctypes.c_double(0.0)
     _check(lib().rt_firefly(device, nx, ny, c.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,
-                            None if m is None else m.ctypes.data, ctypes.byref(fp), out.ctypes.data,
-                            None if om is None else om.ctypes.data, None if ratio is None else ratio.ctypes.data,
-                            ctypes.byref(ms)))
+                            _ptr(m), ctypes.byref(fp), out.ctypes.data, _ptr(om), _ptr(ratio), ctypes.byref(ms)))
     res = [out] + ([om] if om is not None else []) + ([ratio] if want_ratio else []) + ([ms.value] if timing else [])
     return res[0] if len(res) == 1 else tuple(res)
 
@@ -768,9 +774,7 @@ def firefly(color, features, moments=None, *, demodulate=None, radius=None, min_
 # -------------------------------------------------------------- frame history
 def temporal_params(frame_spp, max_history=None, cos_normal=None, sigma_depth=None):
     given = dict(max_history=max_history, cos_normal=cos_normal, sigma_depth=sigma_depth)
-    v = {n: TEMPORAL_DEFAULTS[n] if x is None else x for n, x in given.items()}
-    return RtTemporalParams(max_history=int(v["max_history"]), cos_normal=v["cos_normal"], sigma_depth=v["sigma_depth"],
-                            frame_spp=int(frame_spp))
+    return _params(RtTemporalParams, TEMPORAL_DEFAULTS, ("max_history",), given, frame_spp=int(frame_spp))
 
 
 def pack_guides(features) -> np.ndarray:
@@ -808,9 +812,8 @@ def temporal(color, features, moments, frame_spp, cam: Camera, history=None, pre
     m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
     tp = temporal_params(frame_spp, max_history, cos_normal, sigma_depth)
     out, om, ol = np.zeros_like(c), (None if m is None else np.zeros_like(m)), np.zeros((ny, nx), np.int32)
-    ptr = lambda a: None if a is None else a.ctypes.data
-    cur = RtTemporalFrame(ptr(c), ptr(g), ptr(m), None)
-    dst = RtTemporalFrame(ptr(out), None, ptr(om), ptr(ol))
+    cur = RtTemporalFrame(_ptr(c), _ptr(g), _ptr(m), None)
+    dst = RtTemporalFrame(_ptr(out), None, _ptr(om), _ptr(ol))
     hist, keep = None, None
     if history is not None:
         if prev_cam is None:
@@ -820,7 +823,7 @@ def temporal(color, features, moments, frame_spp, cam: Camera, history=None, pre
                 pack_guides(history["features"]).reshape(ny, nx, 8),
                 None if hm is None else np.ascontiguousarray(hm, np.float32).reshape(ny, nx, 2),
                 np.ascontiguousarray(history["len"], np.int32).reshape(ny, nx))
-        hist = RtTemporalFrame(*(ptr(a) for a in keep))
+        hist = RtTemporalFrame(*(_ptr(a) for a in keep))
     ms = ctypes.c_double(0.0)
     _check(lib().rt_temporal(device, nx, ny, ctypes.byref(cur), ctypes.byref(cam.desc),
                              None if hist is None else ctypes.byref(hist),
@@ -864,7 +867,7 @@ class Dist:
         img = np.zeros((params.ny, params.nx, 3), np.float32) if self.rank == 0 else None
         st = RtStats()
         _check(lib().rt_dist_render(self.handle, scene.handle, ctypes.byref(cam.desc), ctypes.byref(params),
-                                    img.ctypes.data if img is not None else None, ctypes.byref(st)))
+                                    _ptr(img), ctypes.byref(st)))
         return img, st.as_dict()
 
     def close(self):

@@ -573,6 +573,25 @@ void limits() {
     }
 }
 
+// The side units' staging regions (job_plan.h Regions; capi_internal.h Staging): rt_temporal's ten,
+// in its order and in floats, at the smallest and the largest image: each starts where the one
+// before ended (no overlap, no gap) and the total is the sum, without wrapping in size_t.
+void staging_regions() {
+    for (size_t npix : {(size_t)1, (size_t)0x7FFFFFFF}) {
+        const size_t per_pixel[10] = {8, 8, 3, 3, 3, 2, 2, 2, 1, 1};   // guides x 2, colour x 3, moments x 3, len x 2
+        rtnw::Regions plan;
+        size_t sum = 0;
+        for (size_t k : per_pixel) {
+            const rtnw::Region r = plan.add(npix * k);
+            EXPECT(r.at == sum && r.n == npix * k);
+            if (k == 8) EXPECT(r.at % 4 == 0);   // the guides are read by 16-B loads
+            sum += r.n;
+            EXPECT(plan.total == sum);
+        }
+        EXPECT(sum == npix * 33 && sum / 33 == npix && sum * sizeof(float) / sizeof(float) == sum);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -585,6 +604,7 @@ int main(int argc, char **argv) {
     active_orders();
     batch_plans();
     limits();
+    staging_regions();
     std::printf(failures ? "FAILED %d\n" : "OK\n", failures);
     return failures ? 1 : 0;
 }

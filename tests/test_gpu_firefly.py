@@ -81,6 +81,30 @@ def test_firefly_equals_the_statement(nx, ny, radius, demodulate, moments):
         assert len(res) == 2 and want_mom is None
 
 
+@pytest.mark.parametrize("moments,out_moments,ratio", [(1, 1, 1), (1, 1, 0), (1, 0, 1), (1, 0, 0), (0, 0, 1), (0, 0, 0)])
+def test_the_host_form_with_and_without_each_optional_pointer(moments, out_moments, ratio):
+    """rt_firefly itself (rtnw.firefly always asks for the moments it can have) at 67 x 9, a column
+    past a 64-wide block and a row past two 4-row blocks: whatever is asked for equals the
+    statement bit for bit, whatever else is or is not."""
+    nx, ny = 67, 9
+    d = inputs(nx, ny)
+    c, a, n, z, m = (np.ascontiguousarray(d[k], np.float32) for k in ("color", "albedo", "normal", "depth", "moments"))
+    want, want_mom, want_ratio = statement(nx, ny, bool(moments), **SYNTHETIC)
+    fp = rtnw.firefly_params(**SYNTHETIC)
+    out, om, rt = np.zeros((ny, nx, 3), np.float32), np.zeros((ny, nx, 2), np.float32), np.zeros((ny, nx), np.float32)
+    ms = ctypes.c_double(-1.0)
+    rtnw._check(rtnw.lib().rt_firefly(0, nx, ny, c.ctypes.data, a.ctypes.data, n.ctypes.data, z.ctypes.data,
+                                      m.ctypes.data if moments else None, ctypes.byref(fp), out.ctypes.data,
+                                      om.ctypes.data if out_moments else None, rt.ctypes.data if ratio else None,
+                                      ctypes.byref(ms)))
+    check(out, want, "colour")
+    if out_moments:
+        check(om, want_mom, "moments")
+    if ratio:
+        check(rt, want_ratio, "ratio")
+    assert ms.value >= 0.0
+
+
 def test_the_spikes_are_clamped_at_the_border_and_the_block_seam():
     """What the parametrised test compares is not vacuous at the places a tile can go wrong."""
     nx, ny = 130, 9

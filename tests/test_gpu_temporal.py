@@ -99,6 +99,26 @@ def test_temporal_equals_the_statement(nx, ny, inputs, case, moments):
         assert got_mom is None and want_mom is None
 
 
+def test_the_host_form_with_moments_and_no_output_moments():
+    """rt_temporal itself (rtnw.temporal always asks for the moments it can have) on a history
+    with moments and out->moments null, at 67 x 9, a column past a 64-wide block and a row past
+    two 4-row blocks: colour and len equal the statement bit for bit."""
+    nx, ny = 67, 9
+    cur, cam, hist, prev_cam = arguments("planes", nx, ny, "two-cameras", True)
+    want, _, want_len = statement("planes", nx, ny, "two-cameras", True)
+    keep = [np.ascontiguousarray(fr[k], t) for fr in (cur, hist) for k, t in (("color", F), ("features", F), ("moments", F))]
+    keep.append(np.ascontiguousarray(hist["len"], np.int32))
+    out, out_len = np.zeros((ny, nx, 3), F), np.zeros((ny, nx), np.int32)
+    ptr = [a.ctypes.data for a in keep]
+    fcur, fhist = rtnw.RtTemporalFrame(*ptr[0:3], None), rtnw.RtTemporalFrame(*ptr[3:7])
+    fout = rtnw.RtTemporalFrame(out.ctypes.data, None, None, out_len.ctypes.data)
+    tp = rtnw.temporal_params(**SETTINGS)
+    rtnw._check(rtnw.lib().rt_temporal(0, nx, ny, ctypes.byref(fcur), ctypes.byref(cam.desc), ctypes.byref(fhist),
+                                       ctypes.byref(prev_cam.desc), ctypes.byref(tp), ctypes.byref(fout), None))
+    check(out, want, "colour")
+    assert np.array_equal(out_len, want_len), int((out_len != want_len).sum())
+
+
 class DeviceArrays:
     """Device copies of host arrays in one allocation (16-B aligned each), freed on exit."""
 
