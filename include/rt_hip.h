@@ -647,6 +647,90 @@ typedef struct rt_radiance {      /* 16 bytes */
 int rt_radiance_rays    (rt_scene *s, const rt_render_params *p, const rt_path_ray *rays, int64_t n, rt_radiance *out, double *ms);
 int rt_radiance_rays_dev(rt_scene *s, const rt_render_params *p, const rt_path_ray *rays_dev, int64_t n, rt_radiance *out_dev, void *stream);
 
+/* ------------------- lens renders: panorama, fisheye and orthographic cameras */
+enum { RT_LENS_PERSPECTIVE = 0, RT_LENS_ORTHOGRAPHIC = 1, RT_LENS_FISHEYE = 2, RT_LENS_EQUIRECT = 3 };
+typedef struct rt_lens_params {   /* 32 bytes */
+    int32_t model;                /* RT_LENS_* */
+    float   fov_deg;              /* FISHEYE: full angle across the image circle, 0 < fov <= 360; else ignored */
+    int32_t pad[6];               /* zero */
+} rt_lens_params;
+/* A camera model on top of rt_camera_desc: the rays of every (pixel, sample) made on the device
+ * (rt_lens_rays), and the render that feeds them through the radiance query and reduces the
+ * result by the renders' own summation rule (rt_render_lens).  rt_camera_desc (rt_camera_init)
+ * supplies the pose origin, u, v, w and the shutter time0, time1; for PERSPECTIVE also
+ * lower_left_corner, horizontal, vertical and lens_radius, for ORTHOGRAPHIC horizontal and
+ * vertical (the extent of the view).
+ * Records.  rt_lens_rays writes the w x h rectangle's records sample-major: record
+ * k = (sample - sample_offset) * (w * h) + row * w + col, row 0 the top row, for samples
+ * [sample_offset, sample_offset + spp).  Its pixel key is the renders' own, pixel =
+ * (ny - 1 - (y0 + row)) * nx + (x0 + col), its stream sample_key(seed, pixel, sample), and with
+ * x = x0 + col, j = ny - 1 - (y0 + row) the image coordinates are s = (x + draw0) / nx and
+ * t = (j + draw1) / ny, computed as the renders compute them.  The exact float32 statement of
+ * every model, operation order included, is tests/test_lens_spec.py:
+ *   PERSPECTIVE    camera::get_ray exactly (camera.h:41-56): the lens-disk candidates, then the
+ *                  time draw; skip = 5 + 2 * (rejected candidates).
+ *   ORTHOGRAPHIC   origin = (origin + (s - 0.5) horizontal) + (t - 0.5) vertical, dir = -w; no
+ *                  lens draws; skip = 3.
+ *   FISHEYE        equidistant: x = 2s - 1, y = 2t - 1, r = sqrtf(x x + y y), theta = r *
+ *                  (fov_deg * float(pi / 360)), dir = (sin theta x / r) u + (sin theta y / r) v -
+ *                  cos theta w, and -w at r == 0; skip = 3.  A sample with r > 1 lies outside the
+ *                  image circle and has NO RAY: its record carries the direction (0, 0, 0), which
+ *                  the queries report as RT_HIT_INVALID with radiance (0, 0, 0).  By design it
+ *                  counts in the pixel's mean as black and in the guides as a miss (coverage 0),
+ *                  so the corners of a fisheye image are black and the circle's rim is blended.
+ *   EQUIRECT       phi = 2 pi (s - 0.5), el = pi (t - 0.5), dir = (cos el sin phi) u + (sin el) v
+ *                  - (cos el cos phi) w: the image centre looks along -w, the top row up; skip = 3.
+ * Every sine is glibc's sinf, bit for bit (the device's restatement of it); every cosine is that
+ * sine of the complementary angle formed from the pixel coordinate: cos el = sin(pi (1 - t)),
+ * cos phi = sin(2 pi (0.75 - s)), cos theta = sin(float(pi / 2) - theta).  The time of every
+ * model is float(double(time0) + draw * double(time1 - time0)) (camera.h:54); a closed shutter
+ * consumes the draw unused.  trace_rays, when non-NULL, receives the same rays as rt_ray:
+ * t_min = p->t_min, t_max = +inf, the same time; a no-ray sample keeps its zero direction.
+ * Parameters read from p: nx, ny, spp, sample_offset, seed, max_depth, t_min, background; chunk
+ * is ignored (there is one add per sample); any flag is RT_ERR_INVALID.
+ * Render outputs, row-major h x w.  Every sum runs in float32, in sample order, one add per
+ * sample, from 0; the means are the sums times float(1.0 / spp), as rt_render_tile's:
+ *   out_rgb      3 floats per pixel: the mean of the samples' rt_radiance rgb;
+ *   out_moments  2 floats per pixel (NULL: not wanted): sum y and sum y * y, y = (r + g) + b per
+ *                sample, sums as rt_render_tiles_moments writes them at chunk 1;
+ *   out_guides   8 floats per pixel (NULL: not wanted), packed as rt_render_features_dev packs
+ *                them: the mean of the samples' rt_hit albedo, coverage (1 where prim >= 0),
+ *                normal and depth, from rt_trace_rays' search run on trace_rays: asking for the
+ *                guides costs one more lane-per-ray pass.
+ * Contracts.
+ *   Perspective identity: with RT_LENS_PERSPECTIVE the image is rt_render_tile(chunk = 1) bit for
+ *     bit, the moments rt_render_tiles_moments(chunk = 1)'s, the guides rt_render_features_dev's.
+ *   Composition: for every model rt_render_lens is rt_lens_rays' records fed through
+ *     rt_radiance_rays (and its trace_rays through rt_trace_rays) and reduced by the rule above,
+ *     bit for bit; invalid rays, axis-parallel rays and rects follow those queries' terms.
+ *   Independence: the result depends neither on the batch size nor on the tile split (a tile is
+ *     the crop of the frame).
+ * Arguments, all checked before any HIP call, in this order, the offending one named in
+ * rt_last_error(): RT_ERR_INVALID for a null cam, lens, p or required output (rays; out_rgb); a
+ * model outside RT_LENS_*, a nonzero pad, under FISHEYE a fov_deg that is NaN or outside
+ * (0, 360]; nx or ny outside 1..65535, spp < 1, sample_offset + spp above 0xFFFFFFFF; a rectangle
+ * empty or outside the frame; any flag; max_depth < 0, a non-finite t_min, a background outside
+ * RT_BG_*.  The renders then check the scene: RT_ERR_INVALID when it is NULL, RT_ERR_UNSUPPORTED
+ * on a wide BVH (RTNW_BVH_WIDTH 4, 8, 8q) or when the library was linked without the lens, rays
+ * or (for guides) trace unit, and RT_ERR_INVALID when the scene has moving spheres and the
+ * camera's [time0, time1] leaves the scene's span (every sample would come back invalid).
+ * The render works in batches of whole sample planes of a pixel block, at most RTNW_LENS_BATCH
+ * rays each (env; default 2^21, at most 2^24; any value >= 1 works), in a workspace kept with
+ * the scene.  The host forms are synchronous; *ms, when non-NULL, receives the batches' summed
+ * HIP-event time.  The _dev forms take device pointers (records and guides 16-B aligned) and only
+ * enqueue on `stream` (hipStream_t, NULL = default).  Like the radiance queries a lens render
+ * uses the scene's work counter and workspace: calls on one scene must not overlap each other,
+ * a render or a query of that scene. */
+int rt_lens_rays    (int device, const rt_camera_desc *cam, const rt_lens_params *lens, const rt_render_params *p,
+                     int x0, int y0, int w, int h, rt_path_ray *rays, rt_ray *trace_rays);
+int rt_lens_rays_dev(int device, const rt_camera_desc *cam, const rt_lens_params *lens, const rt_render_params *p,
+                     int x0, int y0, int w, int h, rt_path_ray *rays_dev, rt_ray *trace_rays_dev, void *stream);
+int rt_render_lens    (rt_scene *s, const rt_camera_desc *cam, const rt_lens_params *lens, const rt_render_params *p,
+                       int x0, int y0, int w, int h, float *out_rgb, float *out_moments, float *out_guides, double *ms);
+int rt_render_lens_dev(rt_scene *s, const rt_camera_desc *cam, const rt_lens_params *lens, const rt_render_params *p,
+                       int x0, int y0, int w, int h, float *out_rgb_dev, float *out_moments_dev, float *out_guides_dev,
+                       void *stream);
+
 /* Diagnostic: the device's float transcendentals of the path on n host inputs (out: n
  * floats) — fn 0 the megakernel's sinf (texture.h:36, 55), 2 its asinf and 4 its
  * atan2f(a, b) (hitable.h:15-16), all restated from glibc (rt_libm.h); 1, 3, 5 ocml's

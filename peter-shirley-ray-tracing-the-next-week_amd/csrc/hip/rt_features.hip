@@ -4,7 +4,8 @@
 //
 //   rt_features           one lane per (pixel, sample): the camera ray the megakernel builds
 //                         for that sample (the same key, jitter draws, lens-disk loop and time
-//                         draw: rt_kernel.hip camera_begin / camera_finish), its closest
+//                         draw: rt_kernel.hip camera_begin / camera_finish; stated per lane
+//                         in rt_camera.h, which rt_lens.hip shares), its closest
 //                         surface hit under hitable_list's (t, key) rule, and the hit's
 //                         material colour, world normal and distance into a slab.
 //   rt_features_resolve   adds a pixel's samples in sample order (float32) and scales the
@@ -15,39 +16,10 @@
 // like the megakernel.
 #include "rt_features.h"
 #include "rt_device.h"
+#include "rt_camera.h"
 #include "rt_colour.h"
 
 namespace {
-
-// camera.h:41-56 for one sample, sequentially per lane: the draws, in order, are the two
-// jitters, the lens disk's candidates (two draws each, until one is accepted) and the time.
-__device__ __forceinline__ Ray camera_ray(const RtKernelArgs &A, int x, int j, uint32_t sample, uint64_t skey) {
-    Rng g;
-    g.start(sample_key(skey, (uint32_t)j * (uint32_t)A.nx + (uint32_t)x, sample), false);   // uint32_t: no signed overflow
-    const float cu = div_rn((float)((double)x + g.next()), (float)A.nx, A.rnx);   // main.cpp:305-306
-    const float cv = div_rn((float)((double)j + g.next()), (float)A.ny, A.rny);
-    V3 disk;
-    for (;;) {   // camera.h:6-12
-        const bool ok = DiskCand()(g.x, disk);
-        g.skip2();
-        if (ok) break;
-    }
-    CamView C;
-    C.llc = mk(A.llc[0], A.llc[1], A.llc[2]); C.hor = mk(A.hor[0], A.hor[1], A.hor[2]);
-    C.ver = mk(A.ver[0], A.ver[1], A.ver[2]); C.org = mk(A.org[0], A.org[1], A.org[2]);
-    C.cu = mk(A.cu[0], A.cu[1], A.cu[2]); C.cv = mk(A.cv[0], A.cv[1], A.cv[2]);
-    C.t0 = A.ct0; C.t1 = A.ct1; C.lens = A.lens;
-    const V3 rd = scale(C.lens, disk);
-    const V3 offset = add(scale(rd.x, C.cu), scale(rd.y, C.cv));
-    const float span = C.t1 - C.t0;   // camera.h:54; a closed shutter consumes the draw unused
-    double u = 0.0;
-    if (span != 0.0f) u = g.next(); else g.skip();
-    Ray r;
-    r.time = (float)((double)C.t0 + u * (double)span);
-    r.d = sub(sub(add(add(C.llc, scale(cu, C.hor)), scale(cv, C.ver)), C.org), offset);
-    r.o = add(C.org, offset);
-    return r;
-}
 
 __global__ __launch_bounds__(RT_BLOCK) void rt_features(const RtKernelArgs A, int x0, int y0, int w,
                                                         float4 *__restrict__ slab) {

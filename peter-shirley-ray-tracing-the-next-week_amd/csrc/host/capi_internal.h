@@ -122,6 +122,7 @@ struct rt_scene : rtnw::SceneInfo {
     void *stats = nullptr;        // ... which start here
     DevBuf host_out;
     DevBuf trace_ws;              // rt_trace_rays, rt_occluded: one batch of rays, then its results
+    DevBuf lens_ws;               // rt_render_lens: one batch of records, their radiance and, for guides, its rays and hits
     Events<3> ev;
     rt_scene() = default;
     ~rt_scene() {
@@ -149,6 +150,11 @@ struct JobSlots {
 };
 int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p, const int32_t *tiles, int ntiles,
                const JobSlots *js, float *out_dev, float *mom_dev, void *stream_v, rt_stats *stats);
+
+// capi_radiance.cpp, capi_trace.cpp: one launch over n < 2^31 records in device memory, as the
+// queries' _dev forms enqueue it (the lens renders launch both: capi_lens.cpp)
+int radiance_launch(rt_scene *s, const rt_render_params *p, const void *rays_dev, uint32_t n, void *out_dev, hipStream_t stream);
+int trace_launch(const rt_scene *s, const void *rays_dev, uint32_t n, bool any, void *out_dev, hipStream_t stream);
 
 // The host form of a side unit (rt_denoise, rt_firefly, rt_temporal): one device buffer that
 // lives for the call, carved into regions of floats in the order they are declared (an int32

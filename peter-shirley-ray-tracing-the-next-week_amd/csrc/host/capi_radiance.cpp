@@ -35,7 +35,7 @@ static int radiance_check(const char *fn, const rt_scene *s, const rt_render_par
 // One launch over n records.  The search mode is the one the scene's renders use (flat scan, BVH2
 // in LDS, BVH in HBM), except that a BVH2 the ray-source variant's LDS has no room for stays in
 // HBM; the claim sizes are a render's of n one-sample items (rtnw::plan_batch).
-static int radiance_launch(rt_scene *s, const rt_render_params *p, const void *rays_dev, uint32_t n, void *out_dev,
+int radiance_launch(rt_scene *s, const rt_render_params *p, const void *rays_dev, uint32_t n, void *out_dev,
                            hipStream_t stream) {
     RtKernelArgs a{};
     fill_scene_args(s, a);

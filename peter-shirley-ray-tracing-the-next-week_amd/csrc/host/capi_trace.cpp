@@ -21,7 +21,7 @@ static int trace_check(const char *fn, const rt_scene *s, const void *rays, int6
     return RT_OK;
 }
 
-static int trace_launch(const rt_scene *s, const void *rays_dev, uint32_t n, bool any, void *out_dev, hipStream_t stream) {
+int trace_launch(const rt_scene *s, const void *rays_dev, uint32_t n, bool any, void *out_dev, hipStream_t stream) {
     RtKernelArgs a{};   // the scene's arrays only (rt_trace.h)
     fill_scene_args(s, a);
     HIP_TRY(rt_trace_launch.trace(&a, rays_dev, n, s->has_moving ? 1 : 0, s->time0, s->time1, any ? 1 : 0, any ? nullptr : out_dev,

@@ -204,4 +204,35 @@ uint64_t plan_trace_batch(uint64_t n, const char *knob) {
     return std::max<uint64_t>(1, std::min(per, n));
 }
 
+uint64_t lens_batch_limit(const char *knob) {
+    uint64_t limit = RT_LENS_BATCH;
+    if (knob) {
+        const long long v = std::atoll(knob);
+        if (v > 0) limit = std::min<uint64_t>((uint64_t)v, RT_LENS_BATCH_MAX);
+    }
+    return limit;
+}
+
+LensPlan plan_lens(uint64_t npix, uint64_t spp, uint64_t limit) {
+    LensPlan pl{};
+    limit = std::max<uint64_t>(1, limit);
+    pl.pix_per = std::max<uint64_t>(1, std::min(limit, npix));
+    pl.smp_per = std::max<uint64_t>(1, std::min(limit / pl.pix_per, spp));   // whole planes of the block
+    pl.nblocks = (npix + pl.pix_per - 1) / pl.pix_per;
+    pl.nruns = (spp + pl.smp_per - 1) / pl.smp_per;
+    pl.nbatches = pl.nblocks * pl.nruns;
+    pl.rays_per = pl.pix_per * pl.smp_per;
+    return pl;
+}
+
+LensBatch lens_batch(const LensPlan &pl, uint64_t b, uint64_t npix, uint64_t spp) {
+    const uint64_t block = b / pl.nruns, run = b - block * pl.nruns;
+    LensBatch l;
+    l.p0 = block * pl.pix_per;
+    l.np = std::min(pl.pix_per, npix - l.p0);
+    l.s0 = run * pl.smp_per;
+    l.ns = std::min(pl.smp_per, spp - l.s0);
+    return l;
+}
+
 }  // namespace rtnw

@@ -72,6 +72,28 @@ int plan_feature_batches(uint64_t npix, int spp, uint64_t pixel_bytes, uint64_t 
 inline bool ray_count_ok(int64_t n) { return n >= 0 && n <= 0x7FFFFFFFll; }
 uint64_t plan_trace_batch(uint64_t n, const char *knob);
 
+// Lens renders (capi_lens.cpp): the batches of a w x h rectangle's npix pixels times spp samples.
+// A batch is a run of whole sample planes of a pixel block, pixels [p0, p0 + np) (row-major in
+// the rectangle) times samples [s0, s0 + ns) (counted from the call's first), of at most `limit`
+// rays, limit >= 1; lens_batch_limit reads it from RTNW_LENS_BATCH's text (NULL or not a positive
+// number: RT_LENS_BATCH; clipped to 1..RT_LENS_BATCH_MAX, so always below 2^31).  Batch
+// b < nbatches lists the pixel blocks in order and, inside a block, its sample runs in order: a
+// pixel's samples arrive in sample order.
+#define RT_LENS_BATCH (1ull << 21)        // 128 MiB of records and radiance, 320 MiB with the guides' rays and hits
+#define RT_LENS_BATCH_MAX (1ull << 24)
+struct LensPlan {
+    uint64_t pix_per, smp_per;    // pixels per block, samples per run
+    uint64_t nblocks, nruns;      // blocks of the rectangle, runs of the sample range
+    uint64_t nbatches;            // nblocks * nruns
+    uint64_t rays_per;            // pix_per * smp_per: the largest batch
+};
+struct LensBatch {
+    uint64_t p0, np, s0, ns;
+};
+uint64_t lens_batch_limit(const char *knob);
+LensPlan plan_lens(uint64_t npix, uint64_t spp, uint64_t limit);
+LensBatch lens_batch(const LensPlan &pl, uint64_t b, uint64_t npix, uint64_t spp);
+
 // One buffer carved into regions declared one after another (capi_internal.h Staging): add(n)
 // is the next region, n elements from where the one before ended; total is what all of them take.
 struct Region {

@@ -221,6 +221,49 @@ def pack_path_rays(origin, dir, time=0.0, pixel=0, sample=0, skip=0) -> np.ndarr
     return rays
 
 
+class RtLensParams(ctypes.Structure):   # 32 bytes
+    _fields_ = [("model", ctypes.c_int32), ("fov_deg", ctypes.c_float), ("pad", ctypes.c_int32 * 6)]
+
+
+RT_LENS_PERSPECTIVE, RT_LENS_ORTHOGRAPHIC, RT_LENS_FISHEYE, RT_LENS_EQUIRECT = 0, 1, 2, 3
+
+
+def lens_params(model, fov_deg=180.0) -> RtLensParams:
+    """rt_lens_params: a camera model (RT_LENS_*) and, for the fisheye, the full angle across
+    the image circle in degrees."""
+    return RtLensParams(model=int(model), fov_deg=float(fov_deg))
+
+
+def _lens_count(params, w, h):
+    """The records of a w x h rectangle, or ValueError: the arrays are sized before the library
+    checks the arguments."""
+    if w < 1 or h < 1 or params.spp < 1:
+        raise ValueError("w, h and params.spp must be at least 1")
+    return w * h * params.spp
+
+
+def lens_rays_dev(cam, params: RtRenderParams, lens: RtLensParams, x0, y0, w, h, rays_dev_ptr: int,
+                  trace_rays_dev_ptr: int = 0, stream_ptr: int = 0, device: int = 0):
+    """rt_lens_rays_dev: the w x h rectangle's rt_path_ray records (and rt_ray records, when a
+    pointer is given) into device memory, sample-major, enqueued on the stream."""
+    _check(lib().rt_lens_rays_dev(device, ctypes.byref(cam.desc), ctypes.byref(lens), ctypes.byref(params), x0, y0, w, h,
+                                  ctypes.c_void_p(rays_dev_ptr), ctypes.c_void_p(trace_rays_dev_ptr or None),
+                                  ctypes.c_void_p(stream_ptr)))
+
+
+def lens_rays(cam, params: RtRenderParams, lens: RtLensParams, x0, y0, w, h, trace: bool = False, device: int = 0):
+    """rt_lens_rays: the camera model's rays of the w x h rectangle as [spp, h, w] PATH_RAY_DTYPE
+    records (sample s of the call is params.sample_offset + s), made on the device; with trace
+    also the same rays as [spp, h, w] RAY_DTYPE records (t_min = params.t_min, t_max = +inf)."""
+    n = _lens_count(params, w, h)
+    rays = np.zeros(n, PATH_RAY_DTYPE)
+    tr = np.zeros(n, RAY_DTYPE) if trace else None
+    _check(lib().rt_lens_rays(device, ctypes.byref(cam.desc), ctypes.byref(lens), ctypes.byref(params), x0, y0, w, h,
+                              rays.ctypes.data, _ptr(tr)))
+    shape = (params.spp, h, w)
+    return (rays.reshape(shape), tr.reshape(shape)) if trace else rays.reshape(shape)
+
+
 class RtCheckpoint(ctypes.Structure):
     _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32), ("nx", ctypes.c_int32),
                 ("ny", ctypes.c_int32), ("samples_done", ctypes.c_uint32), ("max_depth", ctypes.c_int32),
@@ -301,6 +344,17 @@ def lib():
                                                 ctypes.c_void_p, P(ctypes.c_double)]),
             "rt_radiance_rays_dev": (ctypes.c_int, [ctypes.c_void_p, P(RtRenderParams), ctypes.c_void_p, ctypes.c_int64,
                                                     ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_lens_rays": (ctypes.c_int, [ctypes.c_int, P(RtCameraDesc), P(RtLensParams), P(RtRenderParams), ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_lens_rays_dev": (ctypes.c_int, [ctypes.c_int, P(RtCameraDesc), P(RtLensParams), P(RtRenderParams),
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_render_lens": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtLensParams), P(RtRenderParams),
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_double)]),
+            "rt_render_lens_dev": (ctypes.c_int, [ctypes.c_void_p, P(RtCameraDesc), P(RtLensParams), P(RtRenderParams),
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
             "rt_device_alloc": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, P(ctypes.c_void_p)]),
             "rt_device_free": (ctypes.c_int, [ctypes.c_void_p]),
             "rt_copy_to_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]),
@@ -333,10 +387,10 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass, the denoiser, the firefly clamp, the frame history, the ray queries and the radiance
-        # queries
+        # the feature pass, the denoiser, the firefly clamp, the frame history, the ray queries, the radiance
+        # queries and the lens renders
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
-                    "rt_copy_to_device",
+                    "rt_copy_to_device", "rt_lens_rays", "rt_lens_rays_dev", "rt_render_lens", "rt_render_lens_dev",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
                     "rt_firefly", "rt_firefly_dev", "rt_temporal", "rt_temporal_dev",
                     "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
@@ -691,6 +745,30 @@ class Scene:
         """rt_radiance_rays_dev: n rt_path_ray records in device memory into n rt_radiance records there."""
         _check(lib().rt_radiance_rays_dev(self.handle, ctypes.byref(params), ctypes.c_void_p(rays_dev_ptr), n,
                                           ctypes.c_void_p(out_dev_ptr), ctypes.c_void_p(stream_ptr)))
+
+    def render_lens(self, cam: Camera, params: RtRenderParams, lens: RtLensParams, x0, y0, w, h, moments: bool = False,
+                    guides: bool = False, timing: bool = False):
+        """rt_render_lens: the w x h rectangle through the camera model `lens` (lens_params): the
+        mean radiance [h, w, 3] float32, then — a tuple when more than the image — the moments
+        [h, w, 2] with moments=True, the packed guides [h, w, 8] (pack_guides' layout) with
+        guides=True and the batches' HIP-event ms with timing=True."""
+        _lens_count(params, w, h)
+        out = np.zeros((h, w, 3), np.float32)
+        mom = np.zeros((h, w, 2), np.float32) if moments else None
+        gd = np.zeros((h, w, 8), np.float32) if guides else None
+        ms = ctypes.c_double(0.0)
+        _check(lib().rt_render_lens(self.handle, ctypes.byref(cam.desc), ctypes.byref(lens), ctypes.byref(params), x0, y0, w, h,
+                                    out.ctypes.data, _ptr(mom), _ptr(gd), ctypes.byref(ms)))
+        res = [out] + ([mom] if moments else []) + ([gd] if guides else []) + ([ms.value] if timing else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def render_lens_dev(self, cam: Camera, params: RtRenderParams, lens: RtLensParams, x0, y0, w, h, out_dev_ptr: int,
+                        moments_dev_ptr: int = 0, guides_dev_ptr: int = 0, stream_ptr: int = 0):
+        """rt_render_lens_dev: the same into device memory (3, 2 and 8 floats per pixel; a zero
+        pointer: not wanted), enqueued on the stream."""
+        _check(lib().rt_render_lens_dev(self.handle, ctypes.byref(cam.desc), ctypes.byref(lens), ctypes.byref(params), x0, y0,
+                                        w, h, ctypes.c_void_p(out_dev_ptr), ctypes.c_void_p(moments_dev_ptr or None),
+                                        ctypes.c_void_p(guides_dev_ptr or None), ctypes.c_void_p(stream_ptr)))
 
     def close(self):
         if self.handle:
