@@ -1,4 +1,4 @@
-// rt_device.h — device code of the path-tracing megakernel (rt_kernel.hip): vectors, the counter
+// rt_device.h — device code of the path-tracing megakernel (rt_megakernel.h): vectors, the counter
 // RNG, primitive tests and hit records (the reference's hitable classes), textures
 // and Perlin noise, the BVH node step, and the wave-cooperative samplers.
 // Arithmetic follows the reference's float/double promotions; compiled with
@@ -1407,7 +1407,7 @@ __device__ __forceinline__ void load_media(const RtKernelArgs &A, MediumRec *lds
 
 // One medium's test (constant_medium.h:26-50) against the surface result.
 // kPlain: every medium of the scene is bounded by one plain sphere (the host checked), so the
-// other boundaries' code is left out (rt_kernel.hip refill).
+// other boundaries' code is left out (rt_megakernel.h refill).
 template <bool kCount, bool kInst = true, bool kPlain = false>
 __device__ __forceinline__ void medium_one(const RtKernelArgs &A, const MediumRec &M, int k, const Ray &r, const Recip &rd,
                                            const Recip &ra, uint64_t xk, bool &have, float &best_t,
@@ -1475,7 +1475,7 @@ __device__ __forceinline__ void medium_one(const RtKernelArgs &A, const MediumRe
 }
 
 // Medium k's record from the workgroup's LDS copy (load_media), through an explicit LDS pointer:
-// three broadcast 16-B reads (media_hit, and the ball waves' fused step in rt_kernel.hip).
+// three broadcast 16-B reads (media_hit, and the ball waves' fused step in rt_megakernel.h).
 __device__ __forceinline__ MediumRec lds_medium_rec(const MediumRec *lds_media, int k) {
     typedef unsigned U4v __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) const U4v LdsU4;

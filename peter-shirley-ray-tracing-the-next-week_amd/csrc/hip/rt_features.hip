@@ -4,7 +4,7 @@
 //
 //   rt_features           one lane per (pixel, sample): the camera ray the megakernel builds
 //                         for that sample (the same key, jitter draws, lens-disk loop and time
-//                         draw: rt_kernel.hip camera_begin / camera_finish; stated per lane
+//                         draw: rt_megakernel.h camera_begin / camera_finish; stated per lane
 //                         in rt_camera.h, which rt_lens.hip shares), its closest
 //                         surface hit under hitable_list's (t, key) rule, and the hit's
 //                         material colour, world normal and distance into a slab.

@@ -1,5 +1,5 @@
 // rt_kernel.h — launch interface between the host runtime (capi_*.cpp) and the
-// megakernel (rt_kernel.hip).  Internal to librt_hip.so.
+// megakernel's units (rt_kernel.hip, rt_kernel_fold.hip, rt_kernel_rays.hip).  Internal to librt_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -101,10 +101,10 @@ struct RtKernelArgs {
     int ball_fast;
     float ball_alb[2][3];
     // one bit per job pixel (bit p & 31 of word p >> 5): no primary ray of the pixel can reach a
-    // surface, and the render is one whose such samples refill may finish itself (rt_kernel.hip
+    // surface, and the render is one whose such samples refill may finish itself (rt_megakernel.h
     // refill, empty_pixels.cpp); null: none is (RTNW_EMPTY_FAST=0, or a condition fails)
     const uint32_t *empty_bits;
-    // the ray-source variants (rt_kernel.hip kRays, rt_hip.h rt_radiance_rays): the work items are
+    // the ray-source variants (rt_megakernel.h kRays, rt_hip.h rt_radiance_rays): the work items are
     // nitems ray records (rt_path_ray, 3 x float4 each) and each finished item stores its
     // rt_radiance (one float4) at its own index; rays_moving: the scene has moving spheres, whose
     // boxes cover [rays_t0, rays_t1] only (a ray whose time lies outside is invalid)
@@ -146,10 +146,6 @@ extern "C" hipError_t rt_launch_resolve(const float *slab, uint32_t npix, int nc
                                         const uint32_t *out_index, float *out, hipStream_t stream);
 // mode: 0 plain, 1 count, 2 profile; width: the scene's RtKernelArgs.bvh_width, 0: the flat-scan kernel
 extern "C" hipError_t rt_megakernel_occupancy(int *blocks_per_cu, int mode, int width);
-// Static LDS bytes of the LDS-BVH variant (its dynamic part: nodes + stacks).
-extern "C" int rt_megakernel_lds_static_bytes(void);
-// the largest static LDS (bytes) the compiler gave any LDS-BVH variant (hipFuncGetAttributes), 0 if unknown
-extern "C" int rt_megakernel_lds_static_actual(void);
 // LDS bytes per workgroup of the BVH2-in-LDS variant a scene with `features` (RT_FEAT_*)
 // runs, with traversal stacks of `stack_depth` entries (rt_kernel.hip)
 extern "C" long rt_lds_need_bytes(int features, int stack_depth);

@@ -129,6 +129,8 @@ struct rt_scene : rtnw::SceneInfo {
         if (own_stream) (void)hipStreamDestroy(own_stream);
     }
 };
+// threads per workgroup of the scene's render launches (rt_megakernel.h rt_mega_block)
+inline int block_threads(const rt_scene *s) { return s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK; }
 
 // internal to the library: not among its dynamic symbols
 #pragma GCC visibility push(hidden)

@@ -1,5 +1,5 @@
 // capi_radiance.cpp — radiance queries on caller-supplied rays (rt_hip.h rt_radiance_rays and
-// its _dev form; rt_kernel.hip kRays, rt_kernel_rays.hip): the argument checks
+// its _dev form; rt_megakernel.h kRays, rt_kernel_rays.hip): the argument checks
 // and the launch of the megakernel's ray-source variant.
 #include <cmath>
 

@@ -25,7 +25,7 @@ double algorithmic_bytes(const rt_stats &st, double items, int bvh_width) {
            20.0 * items;
 }
 
-// Waves per LDS workgroup that gather the medium cell's paths (rt_kernel.hip stage 6);
+// Waves per LDS workgroup that gather the medium cell's paths (rt_megakernel.h stage 6);
 // env RTNW_BALL_WAVES (0: none) for A/B runs.  Their ready batch (RTNW_BALL_BATCH) and the
 // busy lanes below which they claim new samples (RTNW_BALL_CLAIM): 56 and 48 against 48 and
 // 64, c4 48.87 -> 48.50 ms, the share of 8 25.20 -> 25.05 ms (profiles/r06/knobs3_ab.log).
@@ -35,7 +35,7 @@ double algorithmic_bytes(const rt_stats &st, double items, int bvh_width) {
 #define RT_BALL_WAVES 2
 #define RT_BALL_BATCH 56
 #define RT_BALL_CLAIM 48
-// The ball waves' fused in-ball step (rt_kernel.hip stage 3): the eligible lanes another trip of
+// The ball waves' fused in-ball step (rt_megakernel.h stage 3): the eligible lanes another trip of
 // its loop needs; env RTNW_BALL_FAST (0: off) for A/B runs.  Scenes whose media do not qualify
 // (scene_lower.cpp ball_fast_media) run without it whatever the setting.  A trip costs the same
 // however few lanes it serves: 40 / 48 / 56 measure alike, 16 and 64 (hardly ever reached)
@@ -183,7 +183,7 @@ int read_counters(rt_scene *s, bool count, bool prof, double items, rt_stats *st
         stats->wave_shade_passes = (double)sh[0];
         stats->wave_shade_kinds = (double)sh[1];
         stats->lane_scatters = (double)sh[2];
-        // the ball waves (rt_kernel.hip stage 6): a variant without them leaves the slots 0
+        // the ball waves (rt_megakernel.h stage 6): a variant without them leaves the slots 0
         unsigned long long b[RT_BALL_N];
         HIP_TRY(hipMemcpy(b, (unsigned long long *)s->stats + RT_STAT_BALL, sizeof b, hipMemcpyDeviceToHost));
         stats->ball_fused_scatters = (double)b[RT_BALL_FUSED];
@@ -329,7 +329,7 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     // max_depth attenuations (16 B each) for every lane of the launch, within the slab
     // budget's default (RTNW_SLAB_BUDGET shapes the sample batches, not this bound)
     const bool fold = (p->flags & RT_FLAG_RIGHT_FOLD) != 0;
-    const uint64_t fold_lanes = (uint64_t)s->grid[0] * (s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK);
+    const uint64_t fold_lanes = (uint64_t)s->grid[0] * block_threads(s);
     const uint64_t fold_bytes = fold ? fold_lanes * (uint64_t)std::max(1, p->max_depth) * sizeof(float4) : 0;
     if (fold) {
         if (p->flags & (RT_FLAG_COUNT | RT_FLAG_PROFILE))
@@ -391,7 +391,7 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     // items claimed) per wave and batch (tools/tail_probe.py --wave-log; diagnostics)
     const char *wave_log_path = prof ? std::getenv("RTNW_WAVE_LOG") : nullptr;
     DevBuf wave_log;   // freed by every return below, error paths included
-    const size_t wave_log_n = (size_t)s->grid[2] * ((s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK) / 64) * RT_WAVE_LOG_WORDS;
+    const size_t wave_log_n = (size_t)s->grid[2] * (block_threads(s) / 64) * RT_WAVE_LOG_WORDS;
     if (wave_log_path) {
         if (int rc = wave_log.reserve(wave_log_n * sizeof(unsigned long long))) return rc;
         HIP_TRY(hipMemsetAsync(wave_log.p, 0, wave_log_n * sizeof(unsigned long long), stream));
@@ -399,7 +399,7 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     a.wave_log = (unsigned long long *)wave_log.p;
     a.fold = fold ? (float4 *)s->fold.p : nullptr;
     a.fold_stride = (uint32_t)fold_lanes;
-    // refill finishes the samples of the job's empty pixels itself (rt_kernel.hip): a tile job of a
+    // refill finishes the samples of the job's empty pixels itself (rt_megakernel.h): a tile job of a
     // scene and camera that allow it (prepare_job, empty_pixels.cpp), one sample per work item (the
     // item is then the sample), no hit before the origin, not the right fold
     const bool empty_fast = s->job_empty && rtnw::empty_fast_render_ok(p->t_min, chunk, p->flags, !js);
@@ -408,7 +408,7 @@ int render_job(rt_scene *s, const rt_camera_desc *cam, const rt_render_params *p
     // vec3::operator/= (vec3.h:134-141): col *= float(1.0 / ns)
     const uint32_t ns_total = sum_in ? p->sample_offset + (uint32_t)p->spp : (uint32_t)p->spp;
     const float k = (float)(1.0 / (double)(float)ns_total);
-    const uint64_t waves = (uint64_t)s->grid[mode] * ((s->lds_nodes ? RT_LDS_BLOCK : RT_BLOCK) / 64);
+    const uint64_t waves = (uint64_t)s->grid[mode] * (block_threads(s) / 64);
     double kernel_ms = 0, resolve_ms = 0;
     // RTNW_CLAIM (x 64 items) and RTNW_TAIL_CLAIMS override the claim sizes (tests, A/B runs); -1: none
     const char *ec = std::getenv("RTNW_CLAIM"), *et = std::getenv("RTNW_TAIL_CLAIMS");

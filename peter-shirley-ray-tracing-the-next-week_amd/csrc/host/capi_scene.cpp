@@ -7,13 +7,24 @@
 
 namespace {
 
+// the cache slot of a width (rt_megakernel_occupancy's: 0 is the flat scan): BVH2, BVH4, flat
+// scan, BVH8, compressed BVH8
+int width_slot(int width) {
+    switch (width) {
+    case 4: return 1;
+    case 0: return 2;
+    case 8: return 3;
+    case RT_BVH_CW8: return 4;
+    default: return 0;
+    }
+}
 // Resident workgroups per CU of the megakernel, per launch mode and BVH width: a
 // property of the code objects, queried once per process.
 hipError_t occupancy(int *mega, int mode, int width) {
     static std::mutex mu;
-    static int cache[3][5] = {};   // [mode][BVH2, BVH4, flat scan, BVH8, compressed BVH8]
+    static int cache[3][5] = {};   // [mode][width_slot]
     std::lock_guard<std::mutex> lock(mu);
-    int &c = cache[mode][width == 4 ? 1 : width == 0 ? 2 : width == 8 ? 3 : width == RT_BVH_CW8 ? 4 : 0];
+    int &c = cache[mode][width_slot(width)];
     if (!c) {
         hipError_t e;
         if ((e = rt_megakernel_occupancy(&c, mode, width)) != hipSuccess) { c = 0; return e; }
@@ -25,7 +36,7 @@ hipError_t occupancy(int *mega, int mode, int width) {
 }  // namespace
 
 // The kernel features (RT_FEAT_*) a scene's launches carry code for: the launcher runs the
-// smallest compiled variant covering them (rt_kernel.hip launch_features).  RTNW_FEAT_ALL=1
+// smallest compiled variant covering them (rt_kernel_launch.h with_variant).  RTNW_FEAT_ALL=1
 // runs the all-feature variant (the one the wide BVHs use): A/B runs only.
 int scene_features(const rt_scene *s) {
     if (const char *e = std::getenv("RTNW_FEAT_ALL"))

@@ -1,6 +1,6 @@
 // empty_pixels.cpp — which pixels of a render job are provably empty: no primary ray of the
 // pixel can reach a surface primitive, so a sample of it is decided by the media alone
-// (rt_kernel.hip refill finishes such samples at the work claim).
+// (rt_megakernel.h refill finishes such samples at the work claim).
 //
 // The test, in double.  A primary ray of pixel (x, y) has the direction
 // D = llc + cu hor + cv ver - org with cu in [x / nx, (x + 1) / nx], cv likewise (main.cpp:
@@ -158,7 +158,7 @@ bool empty_fast_scene_ok(const SceneInfo &s, const rt_camera_desc *cam) {
     if (!(cam->lens_radius == 0.0f)) return false;
     for (int k = 0; k < 3; k++)
         if (cam->origin[k] == 0.0f && std::signbit(cam->origin[k])) return false;
-    // (only the width-2 media variant carries refill's code, rt_kernel.hip kEmptyFast: the scenes
+    // (only the width-2 media variant carries refill's code, rt_megakernel.h kEmptyFast: the scenes
     // with no instance chain, (u, v)-reading material, checker texture or pre-scanned primitive)
     if (!s.media_plain || s.ninstances > 0 || s.has_uv || s.has_checker || s.nprescan > 0 || s.bvh_width != 2) return false;
     CamBasis cb;

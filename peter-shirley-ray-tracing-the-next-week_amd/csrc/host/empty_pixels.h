@@ -13,7 +13,7 @@
 namespace rtnw {
 
 // Whether the samples of a scene's empty pixels, seen through `cam`, may be finished at the
-// work claim (rt_kernel.hip refill) as far as the scene and the camera decide it: a pinhole
+// work claim (rt_megakernel.h refill) as far as the scene and the camera decide it: a pinhole
 // (lens_radius == 0: the ray's origin and direction do not depend on the lens-disk draw), no
 // -0.0f origin component (org + (+-0) keeps its sign only then), every medium bounded by one
 // plain sphere (the only boundary code refill carries; such a boundary does not move, so the

@@ -35,7 +35,7 @@ float fbits(int i) { float f; std::memcpy(&f, &i, 4); return f; }
 
 // Pre-scan (BVH scenes): the largest primitives — box area >= RTNW_PRESCAN_AREA
 // (default 10 %) of the scene box's, at most RT_PRESCAN_MAX — stay out of the BVH
-// and are tested in lockstep before every descent (rt_kernel.hip): a primitive
+// and are tested in lockstep before every descent (rt_megakernel.h): a primitive
 // whose box spans the scene sits at the BVH's root and nearly every ray tests it
 // anyway.  random_motion's ground sphere: c3 55.57 -> 52.15 ms; final()'s six
 // largest (0.5 %: 2-3 % each) 59.08 -> 62.27 ms, so the threshold leaves them in
@@ -134,7 +134,7 @@ bool flat_scan(const rt_scene_desc *d, int bvh_width, std::vector<int> &order, s
     return true;
 }
 
-// Medium cell (BVH modes; rt_kernel.hip stages 3 and 6): a path inside a dense medium
+// Medium cell (BVH modes; rt_megakernel.h stages 3 and 6): a path inside a dense medium
 // scatters there segment after segment (final(): a third of all segments start inside
 // the subsurface sphere), and every segment's closest-hit search starts from the BVH
 // root.  For one medium bounded by a sphere (c, R) — the densest such — the primitives
@@ -277,7 +277,7 @@ std::vector<rt_dmaterial> to_dmaterials(const rt_scene_desc *d, SceneInfo &s) {
     return mats;
 }
 
-// The ball waves' fused in-ball step (rt_kernel.hip stage 3) scatters a path at a medium without
+// The ball waves' fused in-ball step (rt_megakernel.h stage 3) scatters a path at a medium without
 // the shading stage: it is enabled only where that stage would do nothing else for any medium of
 // the scene — each medium's material an isotropic whose texture is the constant resolved above
 // (flag 2; final()'s two) — and the scene has a medium cell.  The constants go to the kernel

@@ -23,7 +23,7 @@ struct SceneInfo {
     // medium cell: primitives [cell_first, cell_first + cell_n) are copies of those near the ball
     int cell_first = 0, cell_n = 0;
     float cell_c[3] = {0, 0, 0}, cell_r2 = 0, cell_rin2 = 0;
-    // the ball waves' fused in-ball step (rt_kernel.hip stage 3) may run: a medium cell, at most
+    // the ball waves' fused in-ball step (rt_megakernel.h stage 3) may run: a medium cell, at most
     // two media, each with an isotropic material whose texture the host resolved to a constant
     // (material flag 2); ball_alb: those constants, in list order
     bool ball_fast = false;

@@ -1,5 +1,5 @@
 // rt_layout.h — the scene's layout in HBM, shared by the host uploader
-// (scene_lower.cpp) and the megakernel (rt_kernel.hip).
+// (scene_lower.cpp) and the megakernel (rt_megakernel.h).
 //
 // Everything the traversal touches is a 16-byte-aligned record read with
 // dwordx4 loads: an incoherent wave fetches one whole record per lane per
@@ -161,7 +161,7 @@ enum {
 // RT_FLAG_PROFILE: cycles in the material scatter branches).
 enum {
     RT_STAT_PROF = RT_CNT_N, RT_STAT_WAVE = RT_CNT_N + 4, RT_STAT_TIME = RT_CNT_N + 9, RT_STAT_SHADE = RT_CNT_N + 16,
-    RT_STAT_BALL = RT_CNT_N + 20,   // RT_FLAG_COUNT, the ball waves (rt_kernel.hip stage 6): RT_BALL_*
+    RT_STAT_BALL = RT_CNT_N + 20,   // RT_FLAG_COUNT, the ball waves (rt_megakernel.h stage 6): RT_BALL_*
     RT_STAT_SAMPLER = RT_CNT_N + 30,   // RT_FLAG_COUNT, the shading stage's rejection sampler: RT_SAMPLER_*
     RT_STAT_EMPTY = RT_CNT_N + 34,     // RT_FLAG_COUNT: samples of empty pixels finished at the work claim (lane-level)
     RT_STATS_LEN = RT_CNT_N + 35
@@ -169,10 +169,10 @@ enum {
 // ball-wave counters: ball-wave iterations, their live lanes and traversal rounds summed over
 // them, segments the medium cell decided (in ball waves), paths a normal wave could not push
 // (the ball's pool full), paths pushed into the ball's pool / the others' pool, paths taken;
-// the fused in-ball step (rt_kernel.hip stage 3), lane-level: the lanes its trips served (the
+// the fused in-ball step (rt_megakernel.h stage 3), lane-level: the lanes its trips served (the
 // segments that scattered there) and the eligible lanes its trips declined (rt_stats
 // ball_fused_scatters, ball_fused_declined)
-// RT_FLAG_PROFILE reuses the RT_STAT_BALL slots with another meaning (rt_kernel.hip's epilogue,
+// RT_FLAG_PROFILE reuses the RT_STAT_BALL slots with another meaning (rt_megakernel.h's epilogue,
 // capi_render.cpp read_counters): [0..3] the ball waves' claim / traverse / media / shade
 // cycles, [4] their iterations, [5] all waves' iterations, [6] the fused in-ball step's trips,
 // [7] those trips' cycles (part of [1]).

@@ -384,7 +384,7 @@ def ball_centre(variant):
 
 
 def ball(b, variant):
-    """The ball waves' fused in-ball step (rt_kernel.hip stage 3) on a BVH scene of more than 64
+    """The ball waves' fused in-ball step (rt_megakernel.h stage 3) on a BVH scene of more than 64
     primitives without an instance chain: one dense sphere-bounded ball of radius BALL_R that
     fills most of the frame, every medium an isotropic of a constant texture (BALL_ALB: distinct,
     no component 0 or 1), the ground and 77 small spheres out of the ball's reach."""
@@ -397,7 +397,7 @@ def ball(b, variant):
         avoid.append((third_c, 0.5 + 0.3))
     if variant == "with_instance":
         avoid.append((np.add(box_at, (0.3, 0.3, 0.3)), 1.0))
-    # The ball waves exist only in the kernel variant of the feature set "media" alone (rt_kernel.hip kBall):
+    # The ball waves exist only in the kernel variant of the feature set "media" alone (rt_megakernel.h kBall):
     # no checker texture, no pre-scanned primitive, no instance chain.  So the ground is a plain 4.8 x 4.8
     # lambertian (box area 46) and the scene box is pinned to 12 x 5.8 x 12 by two spheres in its corners
     # (area 566): neither the ground nor the ball's shell (24) reaches the pre-scan's 10 % of it.

@@ -407,7 +407,7 @@ void active_orders() {
     }
 }
 
-// rt_kernel.hip refill: claim k of a launch covers [base, end) — restated here.
+// rt_megakernel.h refill: claim k of a launch covers [base, end) — restated here.
 void claim_range(const rtnw::BatchLaunch &l, uint64_t k, uint64_t *base, uint64_t *end) {
     const uint64_t big = std::min<uint64_t>(k, l.nbig);
     const uint64_t b64 = big * l.claim + (k - big) * l.claim_tail;

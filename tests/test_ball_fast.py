@@ -1,4 +1,4 @@
-"""The ball waves' fused in-ball step (rt_kernel.hip stage 3, RTNW_BALL_FAST; DESIGN.md §5c
+"""The ball waves' fused in-ball step (rt_megakernel.h stage 3, RTNW_BALL_FAST; DESIGN.md §5c
 round 8).
 
 A ball wave serves the segments that start inside final()'s dense medium, are decided by the

@@ -1,9 +1,9 @@
 """Every compile-time knob of the megakernel builds with a non-default value (VERDICT r05
 item 6: no `#if RT_*` branch that no test compiles).
 
-Each build is device-only (`--cuda-device-only`) with -DRT_KNOB_CHECK, which instantiates
-two variants — final()'s (BVH2 in LDS, media) and cornell_box's (flat scan, instances) —
-instead of the whole variant set, so a knob value compiles in ~3 s.  The meta-test below
+Each build is device-only (`--cuda-device-only`) of csrc/hip/rt_kernel_knobs.hip, which
+instantiates two variants — final()'s (BVH2 in LDS, media) and cornell_box's (flat scan,
+instances) — instead of the whole variant set, so a knob value compiles in ~3 s.  The meta-test below
 fails when a new `#if/#ifdef/#ifndef RT_*` appears in the device sources without a
 value here.  CPU only: hipcc cross-compiles gfx950 without a GPU."""
 import concurrent.futures as cf
@@ -29,16 +29,15 @@ KNOBS = {
     "RT_DESCEND_TAIL_DRY": ["4"],
     "RT_LDS_MEDIA": ["1", "16"],
     "RT_SHADE_LEAN": ["0", "127"],          # every lean bit off / on (2 and 8 spill: off by default)
-    "RT_BALL_POOL": ["8", "64"],            # the ball waves' path pools (rt_kernel.hip stage 6)
+    "RT_BALL_POOL": ["8", "64"],            # the ball waves' path pools (rt_megakernel.h stage 6)
     "RT_NORM_POOL": ["8", "64"],
-    "RT_KNOB_CHECK": [""],                  # this test's own build mode
 }
 
 
 def _build(defs):
     cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
            "-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(PKG, "csrc", "host"), "--offload-arch=gfx950",
-           "-munsafe-fp-atomics", "--cuda-device-only", "-c", "-DRT_KNOB_CHECK", os.path.join(PKG, "csrc", "hip", "rt_kernel.hip"),
+           "-munsafe-fp-atomics", "--cuda-device-only", "-c", os.path.join(PKG, "csrc", "hip", "rt_kernel_knobs.hip"),
            "-o", os.devnull] + defs
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     return r.returncode, r.stderr[-3000:]

@@ -1,4 +1,4 @@
-"""The ball waves' fused in-ball step (rt_kernel.hip stage 3) on the generated ball_* scenes of
+"""The ball waves' fused in-ball step (rt_megakernel.h stage 3) on the generated ball_* scenes of
 tests/gen_scenes.py: the configurations final() never shows it (one medium, the dense medium
 listed second, both media scattering inside the ball, a cell primitive beyond the ball's exit, a
 full cell with a moving sphere, camera rays that start inside the ball with a time of their own,

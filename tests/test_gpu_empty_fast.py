@@ -1,4 +1,4 @@
-"""Camera samples of provably empty pixels finished at the work claim (rt_kernel.hip refill,
+"""Camera samples of provably empty pixels finished at the work claim (rt_megakernel.h refill,
 RTNW_EMPTY_FAST).
 
 refill builds such a sample's pinhole ray, runs the media against t_max = FLT_MAX from the

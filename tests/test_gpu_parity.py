@@ -522,6 +522,47 @@ def test_feature_variants_match_the_all_feature_kernel(monkeypatch, scene, nx, n
     assert np.array_equal(small.view(np.uint32), full.view(np.uint32))
 
 
+# scene -> (its feature variant, <= 64 primitives: scanned by default, its BVH2 has inner nodes to copy to LDS)
+DISPATCH_SCENES = {"final": ("media", False, True), "cornell_box": ("instances", True, True),
+                   "cornell_smoke": ("instances + media", True, True),
+                   "random_scene": ("checker + pre-scan", False, True), "earth": ("all", True, False)}
+
+
+@pytest.mark.parametrize("scene", list(DISPATCH_SCENES))
+def test_count_and_profile_kernels_render_the_plain_image_on_every_route(monkeypatch, scene):
+    """The launch picks a kernel by feature variant (one built-in scene for each of the five),
+    search (flat scan, BVH2 in LDS, BVH in HBM; the wide BVHs' all-feature kernels from HBM) and
+    mode (plain, RT_FLAG_COUNT, RT_FLAG_PROFILE): the counters and the stage clocks only watch,
+    so on every route the count and the profile kernel render the plain kernel's image bit for
+    bit (a kernel of another feature set or search would not: the plain image is held to the
+    all-feature kernel's and to the other searches' above), and rt_stats names the route taken."""
+    variant, small, has_nodes = DISPATCH_SCENES[scene]
+    nx, ny, ns = 32, 32, 4
+    cam_name, bg, depth = rtnw.SCENE_DEFAULTS[scene]
+    cam = rtnw.Camera.preset(cam_name, nx, ny)
+    routes = {("2", "1", "1"): (0.0, True) if small else (1.0, False), ("2", "1", "0"): (float(has_nodes), False),
+              ("2", "0", "0"): (0.0, False), ("4", "1", "1"): (0.0, False), ("8", "1", "1"): (0.0, False),
+              ("8q", "1", "1"): (0.0, False)}
+    for (width, lds, scan), route in routes.items():
+        monkeypatch.setenv("RTNW_BVH_WIDTH", width)
+        monkeypatch.setenv("RTNW_LDS_BVH", lds)
+        monkeypatch.setenv("RTNW_SCAN", scan)
+        sc = rtnw.Scene.builtin(scene, earth_png=O.EARTH_PNG)   # the search is fixed when the scene is built
+        imgs = {}
+        for mode, flags in (("plain", 0), ("count", rtnw.RT_FLAG_COUNT), ("profile", rtnw.RT_FLAG_PROFILE)):
+            p = rtnw.RenderParams(nx, ny, ns, max_depth=depth, background=bg, seed=17, flags=flags)
+            imgs[mode], st = sc.render_tile(cam, p, 0, 0, nx, ny, stats=True)
+            assert (st["lds_level"], st["scan_groups"] > 0) == route, (variant, width, lds, scan, mode)
+            # the mode that ran: only the count kernel counts (samples: its own count, else the host's
+            # product), only the profile kernel reads the clock
+            assert st["samples"] == nx * ny * ns
+            assert (st["segments"] > 0) == (mode == "count"), (variant, width, lds, scan, mode)
+            assert (st["cycles_claim"] > 0) == (mode == "profile"), (variant, width, lds, scan, mode)
+        for mode in ("count", "profile"):
+            assert np.array_equal(imgs[mode].view(np.uint32), imgs["plain"].view(np.uint32)), (variant, width, lds, scan, mode)
+        sc.close()
+
+
 @pytest.mark.parametrize("scene,one_material", [("cornell_box", True), ("final", False)])
 def test_shade_divergence_counters(scene, one_material):
     """RT_FLAG_COUNT's material-divergence counters (lane convergence):
@@ -544,7 +585,7 @@ def test_shade_divergence_counters(scene, one_material):
 
 
 def test_ball_waves_leave_the_image_bitwise_unchanged(monkeypatch):
-    """The ball waves (rt_kernel.hip stage 6) move paths between waves at segment starts
+    """The ball waves (rt_megakernel.h stage 6) move paths between waves at segment starts
     through two LDS pools and end the searches of segments starting inside final()'s dense
     medium at the medium cell's primitives: every sample's draws, adds and slab slot stay
     its own, so the image is the same bit for bit with no ball waves, the default, more

@@ -1,4 +1,4 @@
-"""RT_FLAG_RIGHT_FOLD on the GPU: the megakernel's right-fold variants (rt_kernel.hip kFold).
+"""RT_FLAG_RIGHT_FOLD on the GPU: the megakernel's right-fold variants (rt_megakernel.h kFold).
 
 With the flag a sample's radiance is main.cpp:36's `emitted + attenuation*color(...)`
 evaluated from the deepest hit outwards, the reference's own operation order, so the GPU

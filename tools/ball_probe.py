@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/ball_probe.py [--spp N] — the ball waves' counters (rt_kernel.hip stage 6) on c4:
+"""tools/ball_probe.py [--spp N] — the ball waves' counters (rt_megakernel.h stage 6) on c4:
 one RT_FLAG_COUNT render of final() 500x500 with RTNW_TRACE set (the library prints the
 ball-wave line on stderr) per RTNW_BALL_WAVES value given in --waves."""
 import argparse
