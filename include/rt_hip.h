@@ -539,6 +539,53 @@ int rt_temporal_dev(int device, int nx, int ny, const rt_temporal_frame *cur, co
                     const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
                     const rt_temporal_frame *out, void *stream);
 
+/* ------------------------------- the same with the history clipped to the frame's colour box */
+typedef struct rt_temporal_clamp_params {   /* 32 bytes */
+    int32_t radius;    /* 0..3: half-width of the window of the current frame; 0 = no clamp */
+    float   gamma;     /* >= 0, finite: half-width of the box in standard deviations */
+    int32_t pad[6];    /* zero */
+} rt_temporal_clamp_params;
+/* rt_temporal with variance clipping (Salvi 2016; Karis 2014): between the history fetch and the
+ * blend, a reprojected pixel's history colour c_h is clipped, per channel, to the colour box of
+ * the current frame around the pixel, so that a history that has drifted — resampled at every
+ * reprojection, shaded for an older eye — cannot stray further than the frame allows.  Every
+ * argument of rt_temporal means what it means there; with cp->radius = r >= 1 and unequal
+ * cameras, for a pixel (x, y) that found a history (`use` of the rule above):
+ *   the window is the current frame's colour v at (x + dx, y + dy), dy = -r..r (outer), dx = -r..r
+ *   (inner), every cell inside the image, the centre included; cnt their number, S1 and S2 the
+ *   running sums of v and v * v per channel in that order;
+ *   m = S1 / cnt, var = max(S2 / cnt - m * m, 0), sd = sqrt(var), lo = m - gamma * sd,
+ *   hi = m + gamma * sd, c_h' = c_h < lo ? lo : (c_h > hi ? hi : c_h);
+ *   bit c of the pixel's `clipped` value is set when channel c moved (c_h' != c_h);
+ *   with moments and a nonzero mask the history's per-sample mean moves along and its variance
+ *   stays: y = (c_h0 + c_h1) + c_h2, y' likewise of c_h', mu_1' = max(mu_1 + (y' - y), 0),
+ *   v = max(mu_2 - mu_1 * mu_1, 0), mu_2' = v + mu_1' * mu_1'; with a zero mask they are untouched;
+ *   n_h is unchanged, and the blend runs on c_h', mu_1', mu_2'.
+ * A first frame, bytewise equal cameras (nothing drifts there, and a clamp would bias an exact
+ * running mean) and radius 0 are rt_temporal bit for bit, whatever else cp says, with clipped = 0;
+ * so is a pixel without history.  `clipped` (nx*ny, or NULL) receives the masks.  The exact float32
+ * statement is tests/test_temporal_clamp_spec.py (temporal_clamped_ref).  gamma 0 replaces a
+ * history colour outside the window's mean by that mean; a large gamma never binds.
+ * No setting is suggested for every scene (DESIGN.md §7j records the sweep): at 4 spp a frame
+ * radius 1, gamma 0.5 lowers random_scene's error by 8 % and raises final()'s by 14 %, wider
+ * windows hardly bind; radius 0 is the default of the Python layer.
+ * Host form: as rt_temporal's; `clipped` is a host pointer; *ms is the kernel's time (where nothing
+ * is clamped the mask is zeroed ahead of the timed interval).  Synchronous.
+ * RT_ERR_INVALID: every case of rt_temporal, with its message; then, checked before the device
+ * is touched and named in rt_last_error(), a null cp, radius outside 0..3, gamma negative, NaN
+ * or infinite, a nonzero pad; `clipped` equal to one of the arrays of cur, hist or out (the mask is
+ * a buffer of its own). */
+int rt_temporal_clamped(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                        const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                        const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped, double *ms);
+/* The same with device pointers in the frames and for clipped_dev (or NULL), enqueued on
+ * `stream`; where nothing is clamped, clipped_dev is zeroed on `stream` ahead of the kernel.  No
+ * workspace: calls may overlap; the history sets ping-pong as rt_temporal_dev's. */
+int rt_temporal_clamped_dev(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                            const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                            const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped_dev,
+                            void *stream);
+
 /* ------------------------------- ray queries on the caller's own rays */
 #define RT_HIT_MISS (-1)
 #define RT_HIT_INVALID (-2)

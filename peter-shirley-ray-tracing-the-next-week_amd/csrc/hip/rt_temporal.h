@@ -21,9 +21,29 @@ extern "C" hipError_t rt_launch_temporal(int nx, int ny, int mode, const rt_temp
                                          const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
                                          const rt_temporal_frame *out, hipStream_t stream);
 
-// capi_temporal.cpp reaches the launcher through this table, filled by rt_temporal.hip's static
+// The half-width of the clamp's window is at most this (rt_temporal_clamp_params.radius): the
+// clamped kernel's LDS tile is sized by it.
+#define RT_TEMPORAL_CLAMP_MAX_RADIUS 3
+
+// rt_launch_temporal with the history colour clipped to the colour box of the current frame's
+// neighbourhood (rt_temporal_clamped).  Only mode RT_TEMPORAL_REPROJECT with
+// cp->radius >= 1 runs the clamped kernel (rt_temporal_clamps); every other case runs
+// rt_launch_temporal's and leaves `clipped` alone: the caller zeroes it then, outside what it
+// times.  `clipped` (device, nx * ny, or null; none of the frames' arrays) receives the mask of the
+// channels the clamp moved.  cp has passed capi_temporal.cpp's checks.
+inline bool rt_temporal_clamps(int mode, const rt_temporal_clamp_params *cp) {
+    return mode == RT_TEMPORAL_REPROJECT && cp->radius >= 1;
+}
+extern "C" hipError_t rt_launch_temporal_clamped(int nx, int ny, int mode, const rt_temporal_frame *cur,
+                                                 const rt_camera_desc *cam, const rt_temporal_frame *hist,
+                                                 const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                                                 const rt_temporal_clamp_params *cp, const rt_temporal_frame *out,
+                                                 int32_t *clipped, hipStream_t stream);
+
+// capi_temporal.cpp reaches the launchers through this table, filled by rt_temporal.hip's static
 // initialiser when the unit is linked in (like rt_firefly.h's RtFireflyLaunch).
 struct RtTemporalLaunch {
     decltype(&rt_launch_temporal) accumulate;
+    decltype(&rt_launch_temporal_clamped) accumulate_clamped;
 };
 extern "C" RtTemporalLaunch rt_temporal_launch;   // defined (empty) in capi_temporal.cpp

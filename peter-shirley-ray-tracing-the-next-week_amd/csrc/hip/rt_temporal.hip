@@ -5,6 +5,9 @@
 //                            the previous camera, and takes the history's colour, per-sample
 //                            moments and length from the bilinear taps there whose guides agree
 //                            with its own; with equal cameras from its own pixel, untested.
+//   rt_temporal_accumulate_clamped   the same under unequal cameras with the history colour clipped
+//                            to the colour box of the current frame's neighbourhood:
+//                            the block's pixels and their halo are staged in LDS, the gather stays.
 //
 // One lane per pixel, blocks of 64 x 4, a wave on 64 consecutive pixels of a row.  The pixel's
 // own guides come as two 16-B loads; the four taps are gathered from global memory (two 16-B
@@ -22,6 +25,102 @@ namespace {
 
 __device__ __forceinline__ float dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
     return (a0 * b0 + a1 * b1) + a2 * b2;
+}
+
+// c clipped to mean +- gamma standard deviations of a window of n values with sum S1 and sum of squares S2
+__device__ __forceinline__ float clip_to_box(float c, float S1, float S2, float n, float gamma) {
+    const float m = S1 / n;
+    float var = S2 / n - m * m;
+    var = var < 0.0f ? 0.0f : var;
+    const float sd = sqrtf(var);
+    const float lo = m - gamma * sd, hi = m + gamma * sd;
+    return c < lo ? lo : (c > hi ? hi : c);
+}
+
+// rt_temporal_accumulate's reprojection branch, operation for operation, for the clamped kernel
+// (sharing it with that kernel moved its registers from 79 to 82 VGPRs, so its text stays as it
+// was): the history of pixel (x, y), p = y * nx + x, under unequal cameras.  Sets use, nh, the
+// history colour ch and per-sample moments u where it finds one; leaves them otherwise.
+__device__ __forceinline__ void reproject_history(
+    int x, int y, size_t p, int nx, int ny, bool have, const float4 *__restrict__ cur_guides,
+    const float *__restrict__ h_color, const float4 *__restrict__ h_guides, const float *__restrict__ h_moments,
+    const int32_t *__restrict__ h_len, const rt_camera_desc &cam, const rt_camera_desc &prev, const rt_temporal_params &tp,
+    bool &use, int &nh, float &ch0, float &ch1, float &ch2, float &u1, float &u2) {
+    const float fnx = (float)nx, fny = (float)ny;
+    const float4 A = cur_guides[p * 2], N = cur_guides[p * 2 + 1];
+    if (A.w == 1.0f) {
+        const float s = ((float)x + 0.5f) / fnx, t = ((float)(ny - 1 - y) + 0.5f) / fny;
+        const float e0 = ((cam.lower_left_corner[0] + s * cam.horizontal[0]) + t * cam.vertical[0]) - cam.origin[0];
+        const float e1 = ((cam.lower_left_corner[1] + s * cam.horizontal[1]) + t * cam.vertical[1]) - cam.origin[1];
+        const float e2 = ((cam.lower_left_corner[2] + s * cam.horizontal[2]) + t * cam.vertical[2]) - cam.origin[2];
+        const float k = N.w / sqrtf(dot3(e0, e1, e2, e0, e1, e2));
+        const float d0 = (cam.origin[0] + e0 * k) - prev.origin[0];
+        const float d1 = (cam.origin[1] + e1 * k) - prev.origin[1];
+        const float d2 = (cam.origin[2] + e2 * k) - prev.origin[2];
+        const float dw = dot3(d0, d1, d2, prev.w[0], prev.w[1], prev.w[2]);
+        if (dw < 0.0f) {   // in front of the previous camera
+            const float a0 = prev.lower_left_corner[0] - prev.origin[0];
+            const float a1 = prev.lower_left_corner[1] - prev.origin[1];
+            const float a2 = prev.lower_left_corner[2] - prev.origin[2];
+            const float tau = dot3(a0, a1, a2, prev.w[0], prev.w[1], prev.w[2]) / dw;
+            const float r0 = d0 * tau - a0, r1 = d1 * tau - a1, r2 = d2 * tau - a2;
+            const float sp = dot3(r0, r1, r2, prev.horizontal[0], prev.horizontal[1], prev.horizontal[2]) /
+                             dot3(prev.horizontal[0], prev.horizontal[1], prev.horizontal[2], prev.horizontal[0],
+                                  prev.horizontal[1], prev.horizontal[2]);
+            const float tq = dot3(r0, r1, r2, prev.vertical[0], prev.vertical[1], prev.vertical[2]) /
+                             dot3(prev.vertical[0], prev.vertical[1], prev.vertical[2], prev.vertical[0],
+                                  prev.vertical[1], prev.vertical[2]);
+            const float fx = sp * fnx - 0.5f, fy = (float)(ny - 1) - (tq * fny - 0.5f);
+            const float zp = sqrtf(dot3(d0, d1, d2, d0, d1, d2));
+            const float bx = floorf(fx), by = floorf(fy);
+            const float wx1 = fx - bx, wy1 = fy - by, wx0 = 1.0f - wx1, wy0 = 1.0f - wy1;
+            float W = 0.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, m1 = 0.0f, m2 = 0.0f;
+            int nmin = 0x7FFFFFFF;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const float qxf = bx + (float)i, qyf = by + (float)j;
+                    const float w = (i ? wx1 : wx0) * (j ? wy1 : wy0);
+                    // a NaN or infinite position fails these; only then are the integers taken
+                    bool in = w > 0.0f && qxf >= 0.0f && qxf < fnx && qyf >= 0.0f && qyf < fny;
+                    const int qx = in ? (int)qxf : 0, qy = in ? (int)qyf : 0;
+                    in = in && qx < nx && qy < ny;   // float(nx) may have rounded up
+                    if (in) {
+                        const size_t q = (size_t)qy * nx + qx;
+                        const int lq = h_len[q];
+                        const float4 Aq = h_guides[q * 2], Nq = h_guides[q * 2 + 1];
+                        const float dn = dot3(N.x, N.y, N.z, Nq.x, Nq.y, Nq.z);
+                        const bool ok = lq > 0 && Aq.w == 1.0f && dn >= tp.cos_normal &&
+                                        fabsf(zp - Nq.w) <= tp.sigma_depth * fminf(zp, Nq.w) + 1e-6f;
+                        if (ok) {
+                            W = W + w;
+                            C0 = C0 + w * h_color[q * 3];
+                            C1 = C1 + w * h_color[q * 3 + 1];
+                            C2 = C2 + w * h_color[q * 3 + 2];
+                            if (have) {
+                                const float fl = (float)lq;
+                                m1 = m1 + w * (h_moments[q * 2] / fl);
+                                m2 = m2 + w * (h_moments[q * 2 + 1] / fl);
+                            }
+                            nmin = min(nmin, lq);
+                        }
+                    }
+                }
+            }
+            if (W > 0.0f) {
+                nh = min(nmin, tp.max_history);
+                if (nh > 0) {
+                    use = true;
+                    ch0 = C0 / W;
+                    ch1 = C1 / W;
+                    ch2 = C2 / W;
+                    u1 = m1 / W;
+                    u2 = m2 / W;
+                }
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void rt_temporal_accumulate(
@@ -158,6 +257,113 @@ __global__ __launch_bounds__(256) void rt_temporal_accumulate(
     }
 }
 
+// The clamped form's tile of the current frame's colour: a block's 64 x 4 pixels and a halo of
+// RT_TEMPORAL_CLAMP_MAX_RADIUS on every side, a plane per channel (a wave reads 64 consecutive floats).
+constexpr int TILE_W = 64 + 2 * RT_TEMPORAL_CLAMP_MAX_RADIUS, TILE_H = 4 + 2 * RT_TEMPORAL_CLAMP_MAX_RADIUS;
+
+// rt_temporal_accumulate under unequal cameras with one step between the history fetch and the
+// blend: the history colour is clipped, per channel, to mean +- gamma standard deviations of the
+// current frame's colours within `radius` of the pixel (tests/test_temporal_clamp_spec.py's
+// temporal_clamped_ref).  The window's colours come from the LDS tile; cells outside
+// the image are not read from memory and hold zero.  Every lane of a block stays for the tile loads and the
+// barriers; only lanes on a pixel go further.  R is the window's radius (its loops unroll, and
+// the tile's extent stays out of the SGPRs, which the two cameras fill).
+template <int R>
+__global__ __launch_bounds__(256) void rt_temporal_accumulate_clamped(
+    int nx, int ny, const float *__restrict__ cur_color, const float4 *__restrict__ cur_guides, const float *cur_moments,
+    const float *__restrict__ h_color, const float4 *__restrict__ h_guides, const float *__restrict__ h_moments,
+    const int32_t *__restrict__ h_len, float *__restrict__ o_color, float *o_moments, int32_t *__restrict__ o_len,
+    int32_t *__restrict__ clipped, rt_camera_desc cam, rt_camera_desc prev, rt_temporal_params tp, float gamma) {
+    __shared__ float tile[3][TILE_H][TILE_W];
+    constexpr int r = R, tw = 64 + 2 * r, th = 4 + 2 * r;
+    const int x0 = (int)(blockIdx.x * 64), x = x0 + (int)threadIdx.x;
+    const int tid = (int)(threadIdx.y * 64 + threadIdx.x);
+    const bool have = cur_moments != nullptr;
+    const float nf = (float)tp.frame_spp;
+    // grid.y is capped (rt_launch_temporal_clamped): a block walks the row blocks it stands for
+    for (int64_t yb = (int64_t)blockIdx.y * 4; yb < ny; yb += (int64_t)gridDim.y * 4) {
+        const int y0 = (int)yb, y = y0 + (int)threadIdx.y;
+        __syncthreads();   // the previous row block's window sums are done with the tile
+        for (int i = tid; i < th * tw * 3; i += 256) {   // a tile row is tw * 3 consecutive floats of the frame
+            const int row = i / (tw * 3), rem = i - row * (tw * 3), col = rem / 3, c = rem - col * 3;
+            const int gx = x0 - r + col, gy = y0 - r + row;
+            const bool in = gx >= 0 && gx < nx && gy >= 0 && gy < ny;   // a cell outside the image is not read
+            tile[c][row][col] = in ? cur_color[((size_t)gy * nx + gx) * 3 + c] : 0.0f;
+        }
+        __syncthreads();
+        if (x < nx && y < ny) {
+            const size_t p = (size_t)y * nx + x;
+            const int tx = (int)threadIdx.x + r, ty = (int)threadIdx.y + r;
+            const float cf0 = tile[0][ty][tx], cf1 = tile[1][ty][tx], cf2 = tile[2][ty][tx];
+            float s1 = 0.0f, s2 = 0.0f;
+            if (have) {
+                s1 = cur_moments[p * 2];
+                s2 = cur_moments[p * 2 + 1];
+            }
+            bool use = false;
+            int nh = 0, mask = 0;
+            float ch0 = 0.0f, ch1 = 0.0f, ch2 = 0.0f, u1 = 0.0f, u2 = 0.0f;
+            reproject_history(x, y, p, nx, ny, have, cur_guides, h_color, h_guides, h_moments, h_len, cam, prev, tp, use, nh,
+                              ch0, ch1, ch2, u1, u2);
+            if (use) {
+                // cells outside the image hold zero: S + 0 is S bit for bit (a sum that starts at +0 is never -0),
+                // so every cell of the window is added and only the count knows the border
+                const int cnt = (min(x + r, nx - 1) - max(x - r, 0) + 1) * (min(y + r, ny - 1) - max(y - r, 0) + 1);
+                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, q0 = 0.0f, q1 = 0.0f, q2 = 0.0f;
+#pragma unroll
+                for (int dy = -r; dy <= r; ++dy) {
+#pragma unroll
+                    for (int dx = -r; dx <= r; ++dx) {
+                        const float v0 = tile[0][ty + dy][tx + dx], v1 = tile[1][ty + dy][tx + dx], v2 = tile[2][ty + dy][tx + dx];
+                        a0 = a0 + v0;
+                        a1 = a1 + v1;
+                        a2 = a2 + v2;
+                        q0 = q0 + v0 * v0;
+                        q1 = q1 + v1 * v1;
+                        q2 = q2 + v2 * v2;
+                    }
+                }
+                const float fc = (float)cnt;
+                const float k0 = clip_to_box(ch0, a0, q0, fc, gamma), k1 = clip_to_box(ch1, a1, q1, fc, gamma),
+                            k2 = clip_to_box(ch2, a2, q2, fc, gamma);
+                mask = (k0 != ch0 ? 1 : 0) | (k1 != ch1 ? 2 : 0) | (k2 != ch2 ? 4 : 0);
+                if (have && mask) {   // the mean moves with the colour, the per-sample variance stays
+                    const float yo = (ch0 + ch1) + ch2, yn = (k0 + k1) + k2;
+                    float w1 = u1 + (yn - yo);
+                    w1 = w1 < 0.0f ? 0.0f : w1;
+                    float v = u2 - u1 * u1;
+                    v = v < 0.0f ? 0.0f : v;
+                    u1 = w1;
+                    u2 = v + w1 * w1;
+                }
+                ch0 = k0;
+                ch1 = k1;
+                ch2 = k2;
+            }
+            float o0 = cf0, o1 = cf1, o2 = cf2, om1 = s1, om2 = s2;   // no history: the frame bit for bit
+            int n = tp.frame_spp;
+            if (use) {
+                n = nh + tp.frame_spp;   // below 2^24: float(n) is exact
+                const float fn = (float)n, a = nf / fn;
+                o0 = ch0 + (cf0 - ch0) * a;
+                o1 = ch1 + (cf1 - ch1) * a;
+                o2 = ch2 + (cf2 - ch2) * a;
+                om1 = (u1 + (s1 / nf - u1) * a) * fn;
+                om2 = (u2 + (s2 / nf - u2) * a) * fn;
+            }
+            o_color[p * 3] = o0;
+            o_color[p * 3 + 1] = o1;
+            o_color[p * 3 + 2] = o2;
+            o_len[p] = n;
+            if (o_moments) {   // may be cur's moments: a lane reads and writes its own pixel only
+                o_moments[p * 2] = om1;
+                o_moments[p * 2 + 1] = om2;
+            }
+            if (clipped) clipped[p] = mask;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" hipError_t rt_launch_temporal(int nx, int ny, int mode, const rt_temporal_frame *cur, const rt_camera_desc *cam,
@@ -177,5 +383,27 @@ extern "C" hipError_t rt_launch_temporal(int nx, int ny, int mode, const rt_temp
     return hipGetLastError();
 }
 
-// the unit announces its launcher to the host when it is linked in
-static const bool temporal_unit_linked = (rt_temporal_launch = RtTemporalLaunch{rt_launch_temporal}, true);
+extern "C" hipError_t rt_launch_temporal_clamped(int nx, int ny, int mode, const rt_temporal_frame *cur,
+                                                 const rt_camera_desc *cam, const rt_temporal_frame *hist,
+                                                 const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                                                 const rt_temporal_clamp_params *cp, const rt_temporal_frame *out,
+                                                 int32_t *clipped, hipStream_t stream) {
+    if (nx <= 0 || ny <= 0) return hipSuccess;
+    if (cp->radius < 0 || cp->radius > RT_TEMPORAL_CLAMP_MAX_RADIUS) return hipErrorInvalidValue;   // the tile's halo
+    // nothing is clamped: rt_temporal itself (the caller has zeroed `clipped`)
+    if (!rt_temporal_clamps(mode, cp)) return rt_launch_temporal(nx, ny, mode, cur, cam, hist, prev_cam, tp, out, stream);
+    if (!hist || !prev_cam) return hipErrorInvalidValue;
+    const int64_t rows = ((int64_t)ny + 3) / 4;
+    const dim3 grid((unsigned)(((int64_t)nx + 63) / 64), (unsigned)(rows < 65535 ? rows : 65535)), block(64, 4);
+    const auto kernel = cp->radius == 1 ? rt_temporal_accumulate_clamped<1>
+                        : cp->radius == 2 ? rt_temporal_accumulate_clamped<2> : rt_temporal_accumulate_clamped<3>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, nx, ny, cur->color, (const float4 *)cur->guides, cur->moments,
+                       hist->color, (const float4 *)hist->guides, cur->moments ? hist->moments : nullptr, hist->len,
+                       (float *)out->color, cur->moments ? (float *)out->moments : nullptr, (int32_t *)out->len, clipped, *cam,
+                       *prev_cam, *tp, cp->gamma);
+    return hipGetLastError();
+}
+
+// the unit announces its launchers to the host when it is linked in
+static const bool temporal_unit_linked =
+    (rt_temporal_launch = RtTemporalLaunch{rt_launch_temporal, rt_launch_temporal_clamped}, true);

@@ -1,5 +1,6 @@
 // capi_temporal.cpp — the reprojected frame history that runs ahead of the denoiser
-// (rt_temporal.hip; rt_hip.h): the argument checks, rt_temporal_dev and the host form.
+// (rt_temporal.hip; rt_hip.h): the argument checks, rt_temporal_dev and the host
+// form, and the same two over the clamped launcher (rt_temporal_clamped).
 #include <cmath>
 #include <cstring>
 
@@ -8,7 +9,7 @@
 #include "../hip/rt_temporal.h"
 
 // the unit's launcher, set by its static initialiser (rt_temporal.h)
-RtTemporalLaunch rt_temporal_launch = {nullptr};
+RtTemporalLaunch rt_temporal_launch = {nullptr, nullptr};
 
 // All before any HIP call, the parameter named in the message.
 static int temporal_check(const char *fn, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
@@ -51,10 +52,78 @@ static int temporal_check(const char *fn, int nx, int ny, const rt_temporal_fram
     return RT_OK;
 }
 
+// rt_temporal_clamped's checks: rt_temporal's, then the clamp's own.
+static int temporal_clamp_check(const char *fn, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                                const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                                const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, const int32_t *clipped) {
+    if (int rc = temporal_check(fn, nx, ny, cur, cam, hist, prev_cam, tp, out)) return rc;
+    const std::string f(fn);
+    if (!cp) return fail(RT_ERR_INVALID, f + ": null argument (cp)");
+    if (cp->radius < 0 || cp->radius > RT_TEMPORAL_CLAMP_MAX_RADIUS) return fail(RT_ERR_INVALID, f + ": radius must be in 0..3");
+    if (!(cp->gamma >= 0.0f) || std::isinf(cp->gamma))
+        return fail(RT_ERR_INVALID, f + ": gamma must not be negative, NaN or infinite");
+    for (int32_t w : cp->pad)
+        if (w) return fail(RT_ERR_INVALID, f + ": pad of the clamp's parameters must be zero");
+    if (clipped) {   // written while the frames are read and `out` is written: a buffer of its own
+        const void *c = clipped;
+        const rt_temporal_frame none = {nullptr, nullptr, nullptr, nullptr};
+        for (const rt_temporal_frame *fr : {cur, hist ? hist : &none, out})
+            if (c == fr->color || c == fr->guides || c == fr->moments || c == fr->len)
+                return fail(RT_ERR_INVALID, f + ": clipped must not be one of the frames' arrays");
+    }
+    if (!rt_temporal_launch.accumulate_clamped) return unit_missing(f, "temporal", "rt_temporal.o");
+    return RT_OK;
+}
+
 // Bytewise equal cameras: a pixel's history is its own pixel (rt_hip.h).
 static int temporal_mode(const rt_temporal_frame *hist, const rt_camera_desc *cam, const rt_camera_desc *prev_cam) {
     if (!hist) return RT_TEMPORAL_FIRST;
     return std::memcmp(cam, prev_cam, sizeof(rt_camera_desc)) == 0 ? RT_TEMPORAL_STATIC : RT_TEMPORAL_REPROJECT;
+}
+
+// The host form of both entry points, the checks made: every array staged in one allocation, the
+// kernel timed alone.  `cp` null is rt_temporal; with it, `clipped` (or null) is staged back too.
+static int temporal_host(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                         const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                         const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped, double *ms) {
+    HIP_TRY(hipSetDevice(device));
+    const size_t npix = (size_t)nx * ny;
+    // in floats (an int32 count takes a float's room); the guides first: 16-B loads
+    const size_t g = npix * RT_GUIDE_FLOATS, c = npix * 3, m = npix * 2, l = npix;
+    Staging st;
+    const auto cur_g = st.floats(g), hist_g = st.floats(g), cur_c = st.floats(c), hist_c = st.floats(c), out_c = st.floats(c),
+               cur_m = st.floats(m), hist_m = st.floats(m), out_m = st.floats(m), hist_l = st.floats(l), out_l = st.floats(l),
+               clip = st.floats(clipped ? l : 0);
+    RT_TRY(st.reserve());
+    RT_TRY(st.upload(cur_g, cur->guides));
+    RT_TRY(st.upload(cur_c, cur->color));
+    RT_TRY(st.upload(cur_m, cur->moments));
+    if (hist) {
+        RT_TRY(st.upload(hist_g, hist->guides));
+        RT_TRY(st.upload(hist_c, hist->color));
+        RT_TRY(st.upload(hist_m, cur->moments ? hist->moments : nullptr));
+        RT_TRY(st.upload(hist_l, hist->len));
+    }
+    const rt_temporal_frame dcur = {st.ptr(cur_c), st.ptr(cur_g), st.ptr_if(cur->moments, cur_m), nullptr};
+    const rt_temporal_frame dhist = {st.ptr(hist_c), st.ptr(hist_g), st.ptr_if(cur->moments, hist_m),
+                                     (const int32_t *)st.ptr(hist_l)};
+    const rt_temporal_frame dout = {st.ptr(out_c), nullptr, st.ptr_if(out->moments, out_m), (const int32_t *)st.ptr(out_l)};
+    const int mode = temporal_mode(hist, cam, prev_cam);
+    if (cp && clipped && !rt_temporal_clamps(mode, cp))   // rt_temporal's kernel runs: no channel is clipped
+        HIP_TRY(hipMemsetAsync(st.ptr(clip), 0, npix * sizeof(int32_t), nullptr));
+    RT_TRY(st.begin());   // the events bracket the kernel alone
+    if (cp)
+        HIP_TRY(rt_temporal_launch.accumulate_clamped(nx, ny, mode, &dcur, cam, hist ? &dhist : nullptr, prev_cam, tp, cp, &dout,
+                                                      (int32_t *)st.ptr_if(clipped, clip), nullptr));
+    else
+        HIP_TRY(rt_temporal_launch.accumulate(nx, ny, mode, &dcur, cam, hist ? &dhist : nullptr, prev_cam, tp, &dout, nullptr));
+    RT_TRY(st.end());
+    // the output frame's pointers are written through (rt_hip.h)
+    RT_TRY(st.download((float *)out->color, out_c));
+    RT_TRY(st.download((float *)out->moments, out_m));
+    RT_TRY(st.download((int32_t *)out->len, out_l));
+    RT_TRY(st.download(clipped, clip));
+    return st.elapsed(ms);
 }
 
 extern "C" {
@@ -73,36 +142,28 @@ int rt_temporal(int device, int nx, int ny, const rt_temporal_frame *cur, const 
                 const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
                 const rt_temporal_frame *out, double *ms) {
     if (int rc = temporal_check("rt_temporal", nx, ny, cur, cam, hist, prev_cam, tp, out)) return rc;
+    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, nullptr, out, nullptr, ms);
+}
+
+int rt_temporal_clamped_dev(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                            const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                            const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped_dev,
+                            void *stream) {
+    if (int rc = temporal_clamp_check("rt_temporal_clamped_dev", nx, ny, cur, cam, hist, prev_cam, tp, cp, out, clipped_dev)) return rc;
     HIP_TRY(hipSetDevice(device));
-    const size_t npix = (size_t)nx * ny;
-    // in floats (an int32 count takes a float's room); the guides first: 16-B loads
-    const size_t g = npix * RT_GUIDE_FLOATS, c = npix * 3, m = npix * 2, l = npix;
-    Staging st;
-    const auto cur_g = st.floats(g), hist_g = st.floats(g), cur_c = st.floats(c), hist_c = st.floats(c), out_c = st.floats(c),
-               cur_m = st.floats(m), hist_m = st.floats(m), out_m = st.floats(m), hist_l = st.floats(l), out_l = st.floats(l);
-    RT_TRY(st.reserve());
-    RT_TRY(st.upload(cur_g, cur->guides));
-    RT_TRY(st.upload(cur_c, cur->color));
-    RT_TRY(st.upload(cur_m, cur->moments));
-    if (hist) {
-        RT_TRY(st.upload(hist_g, hist->guides));
-        RT_TRY(st.upload(hist_c, hist->color));
-        RT_TRY(st.upload(hist_m, cur->moments ? hist->moments : nullptr));
-        RT_TRY(st.upload(hist_l, hist->len));
-    }
-    const rt_temporal_frame dcur = {st.ptr(cur_c), st.ptr(cur_g), st.ptr_if(cur->moments, cur_m), nullptr};
-    const rt_temporal_frame dhist = {st.ptr(hist_c), st.ptr(hist_g), st.ptr_if(cur->moments, hist_m),
-                                     (const int32_t *)st.ptr(hist_l)};
-    const rt_temporal_frame dout = {st.ptr(out_c), nullptr, st.ptr_if(out->moments, out_m), (const int32_t *)st.ptr(out_l)};
-    RT_TRY(st.begin());
-    HIP_TRY(rt_temporal_launch.accumulate(nx, ny, temporal_mode(hist, cam, prev_cam), &dcur, cam, hist ? &dhist : nullptr,
-                                          prev_cam, tp, &dout, nullptr));
-    RT_TRY(st.end());
-    // the output frame's pointers are written through (rt_hip.h)
-    RT_TRY(st.download((float *)out->color, out_c));
-    RT_TRY(st.download((float *)out->moments, out_m));
-    RT_TRY(st.download((int32_t *)out->len, out_l));
-    return st.elapsed(ms);
+    const int mode = temporal_mode(hist, cam, prev_cam);
+    if (clipped_dev && !rt_temporal_clamps(mode, cp))   // rt_temporal's kernel runs: no channel is clipped
+        HIP_TRY(hipMemsetAsync(clipped_dev, 0, (size_t)nx * ny * sizeof(int32_t), (hipStream_t)stream));
+    HIP_TRY(rt_temporal_launch.accumulate_clamped(nx, ny, mode, cur, cam, hist, prev_cam, tp, cp, out, clipped_dev,
+                                                  (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_temporal_clamped(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                        const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                        const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped, double *ms) {
+    if (int rc = temporal_clamp_check("rt_temporal_clamped", nx, ny, cur, cam, hist, prev_cam, tp, cp, out, clipped)) return rc;
+    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, cp, out, clipped, ms);
 }
 
 }  // extern "C"

@@ -157,6 +157,16 @@ class RtTemporalParams(ctypes.Structure):   # 32 bytes
 TEMPORAL_DEFAULTS = dict(max_history=16, cos_normal=0.9, sigma_depth=0.1)
 
 
+class RtTemporalClampParams(ctypes.Structure):   # 32 bytes
+    _fields_ = [("radius", ctypes.c_int32), ("gamma", ctypes.c_float), ("pad", ctypes.c_int32 * 6)]
+
+
+# the clamped frame history's settings when none are given: no clamp.  DESIGN.md §7j records the sweep: no radius
+# and gamma served random_scene without costing final() more, so radius 0 it is (radius 1, gamma 0.5 is the
+# setting that gains on random_scene)
+TEMPORAL_CLAMP_DEFAULTS = dict(max_history=16, radius=0, gamma=1.0)
+
+
 class RtRay(ctypes.Structure):   # 48 bytes
     _fields_ = [("origin", ctypes.c_float * 3), ("t_min", ctypes.c_float), ("dir", ctypes.c_float * 3),
                 ("t_max", ctypes.c_float), ("time", ctypes.c_float), ("pad", ctypes.c_float * 3)]
@@ -332,6 +342,14 @@ def lib():
             "rt_temporal_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame), P(RtCameraDesc),
                                                P(RtTemporalFrame), P(RtCameraDesc), P(RtTemporalParams),
                                                P(RtTemporalFrame), ctypes.c_void_p]),
+            "rt_temporal_clamped": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame),
+                                                   P(RtCameraDesc), P(RtTemporalFrame), P(RtCameraDesc), P(RtTemporalParams),
+                                                   P(RtTemporalClampParams), P(RtTemporalFrame), ctypes.c_void_p,
+                                                   P(ctypes.c_double)]),
+            "rt_temporal_clamped_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame),
+                                                       P(RtCameraDesc), P(RtTemporalFrame), P(RtCameraDesc),
+                                                       P(RtTemporalParams), P(RtTemporalClampParams), P(RtTemporalFrame),
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
             "rt_trace_rays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                              P(ctypes.c_double)]),
             "rt_trace_rays_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -387,13 +405,13 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass, the denoiser, the firefly clamp, the frame history, the ray queries, the radiance
-        # queries and the lens renders
+        # the feature pass, the denoiser, the firefly clamp, the frame history and its clamped form, the ray
+        # queries, the radiance queries and the lens renders
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
                     "rt_copy_to_device", "rt_lens_rays", "rt_lens_rays_dev", "rt_render_lens", "rt_render_lens_dev",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
                     "rt_firefly", "rt_firefly_dev", "rt_temporal", "rt_temporal_dev",
-                    "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
+                    "rt_temporal_clamped", "rt_temporal_clamped_dev", "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
                     "rt_radiance_rays", "rt_radiance_rays_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
@@ -873,22 +891,17 @@ def pack_guides(features) -> np.ndarray:
     return g
 
 
-def temporal(color, features, moments, frame_spp, cam: Camera, history=None, prev_cam: Camera | None = None, *,
-             max_history=None, cos_normal=None, sigma_depth=None, device: int = 0, timing: bool = False):
-    """Temporal accumulation (rt_temporal) of the frame `color` [ny, nx, 3] of `frame_spp`
-    samples per pixel, rendered through `cam`, to run ahead of `denoise`: `features` is
-    Scene.render_features' dict (with its coverage) or the packed guides, `moments` [ny, nx, 2]
-    or None.  `history` is None for a first frame, else a dict of the previous call's results
-    and that frame's features: color, moments (None when this call has none), len and features,
-    seen through `prev_cam`.  Every frame must draw fresh samples (sample_offset advanced by
-    frame_spp).  Unset settings take TEMPORAL_DEFAULTS.  Returns (color, moments or None, len):
-    len [ny, nx] int32 is what `denoise` takes as its spp map (and the kernel's ms after them
-    with timing=True)."""
+def temporal_clamp_params(radius=None, gamma=None):
+    return _params(RtTemporalClampParams, TEMPORAL_CLAMP_DEFAULTS, ("radius",), dict(radius=radius, gamma=gamma))
+
+
+def _temporal(color, features, moments, cam, history, prev_cam, tp, cp, device):
+    """rt_temporal (cp None) or rt_temporal_clamped on host arrays: (color, moments or None, len,
+    clipped or None, the kernel's ms)."""
     c = np.ascontiguousarray(color, np.float32)
     ny, nx, _ = c.shape
     g = pack_guides(features).reshape(ny, nx, 8)
     m = None if moments is None else np.ascontiguousarray(moments, np.float32).reshape(ny, nx, 2)
-    tp = temporal_params(frame_spp, max_history, cos_normal, sigma_depth)
     out, om, ol = np.zeros_like(c), (None if m is None else np.zeros_like(m)), np.zeros((ny, nx), np.int32)
     cur = RtTemporalFrame(_ptr(c), _ptr(g), _ptr(m), None)
     dst = RtTemporalFrame(_ptr(out), None, _ptr(om), _ptr(ol))
@@ -903,11 +916,46 @@ def temporal(color, features, moments, frame_spp, cam: Camera, history=None, pre
                 np.ascontiguousarray(history["len"], np.int32).reshape(ny, nx))
         hist = RtTemporalFrame(*(_ptr(a) for a in keep))
     ms = ctypes.c_double(0.0)
-    _check(lib().rt_temporal(device, nx, ny, ctypes.byref(cur), ctypes.byref(cam.desc),
-                             None if hist is None else ctypes.byref(hist),
-                             None if prev_cam is None else ctypes.byref(prev_cam.desc), ctypes.byref(tp), ctypes.byref(dst),
-                             ctypes.byref(ms)))
-    return (out, om, ol, ms.value) if timing else (out, om, ol)
+    head = (device, nx, ny, ctypes.byref(cur), ctypes.byref(cam.desc), None if hist is None else ctypes.byref(hist),
+            None if prev_cam is None else ctypes.byref(prev_cam.desc), ctypes.byref(tp))
+    clipped = None
+    if cp is None:
+        _check(lib().rt_temporal(*head, ctypes.byref(dst), ctypes.byref(ms)))
+    else:
+        clipped = np.zeros((ny, nx), np.int32)
+        _check(lib().rt_temporal_clamped(*head, ctypes.byref(cp), ctypes.byref(dst), clipped.ctypes.data, ctypes.byref(ms)))
+    return out, om, ol, clipped, ms.value
+
+
+def temporal(color, features, moments, frame_spp, cam: Camera, history=None, prev_cam: Camera | None = None, *,
+             max_history=None, cos_normal=None, sigma_depth=None, device: int = 0, timing: bool = False):
+    """Temporal accumulation (rt_temporal) of the frame `color` [ny, nx, 3] of `frame_spp`
+    samples per pixel, rendered through `cam`, to run ahead of `denoise`: `features` is
+    Scene.render_features' dict (with its coverage) or the packed guides, `moments` [ny, nx, 2]
+    or None.  `history` is None for a first frame, else a dict of the previous call's results
+    and that frame's features: color, moments (None when this call has none), len and features,
+    seen through `prev_cam`.  Every frame must draw fresh samples (sample_offset advanced by
+    frame_spp).  Unset settings take TEMPORAL_DEFAULTS.  Returns (color, moments or None, len):
+    len [ny, nx] int32 is what `denoise` takes as its spp map (and the kernel's ms after them
+    with timing=True)."""
+    tp = temporal_params(frame_spp, max_history, cos_normal, sigma_depth)
+    out, om, ol, _, ms = _temporal(color, features, moments, cam, history, prev_cam, tp, None, device)
+    return (out, om, ol, ms) if timing else (out, om, ol)
+
+
+def temporal_clamped(color, features, moments, frame_spp, cam: Camera, history=None, prev_cam: Camera | None = None, *,
+                     radius=None, gamma=None, max_history=None, cos_normal=None, sigma_depth=None, device: int = 0,
+                     timing: bool = False):
+    """`temporal` with the reprojected history colour clipped to the colour box of the frame's
+    neighbourhood (rt_temporal_clamped): the window's mean +- `gamma` standard deviations per
+    channel, over the pixels within `radius` (0..3; 0 is `temporal` itself).  Unset radius, gamma
+    and max_history take TEMPORAL_CLAMP_DEFAULTS, the others TEMPORAL_DEFAULTS.  Returns (color,
+    moments or None, len, clipped): clipped [ny, nx] int32 has bit c set where channel c of the
+    pixel's history colour was moved (and the kernel's ms after them with timing=True)."""
+    tp = temporal_params(frame_spp, TEMPORAL_CLAMP_DEFAULTS["max_history"] if max_history is None else max_history,
+                         cos_normal, sigma_depth)
+    res = _temporal(color, features, moments, cam, history, prev_cam, tp, temporal_clamp_params(radius, gamma), device)
+    return res if timing else res[:4]
 
 
 # ------------------------------------------------------------ multi-GPU (RCCL)

@@ -22,10 +22,22 @@ DESIGN.md §7h).
    once, every output written once — and the GB/s that makes.
 
 Writes <out>/temporal_probe.json and <out>/temporal_probe.md.  Not run by any test.
+
+--clamp measures rt_temporal_clamped over the same camera moves instead: per frame
+the gamma RMS of the accumulated image for every max_history of --max-history, unclamped
+(rt_temporal) and clamped at every radius of --radius and gamma of --gamma, each setting carrying
+its own history, with the share of the pixels whose history the clamp moved; the unclamped
+accumulation at max_history 16, the yardstick, once more on frames drawn with another seed
+(--seed + 1), whose distance from the first run is the spread a difference must exceed to mean
+anything; and the kernel's time for a reprojected frame, rt_temporal's and the clamped entry
+point's at radius 1, 2 and 3.  Writes
+<out>/temporal_clamp_probe.md and .json (the table's numbers; per frame only the unclamped and
+the tightest box's series).
 """
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 
@@ -93,6 +105,132 @@ def run_scene(scene, args):
     return dict(scene=scene, frames=rows, kernel_ms=times)
 
 
+def clamp_scene(scene, args):
+    _, bg, depth = rtnw.SCENE_DEFAULTS[scene]
+    sc = rtnw.Scene.builtin(scene)
+    settings = [(h, 0, 0.0) for h in args.max_history] + \
+               [(h, r, g) for h in args.max_history for r in args.radius for g in args.gamma]
+    hist = {s: None for s in settings}
+    repeat_hist, prev_cam, rows = None, None, []
+    for k in range(args.frames):
+        cam = camera(scene, k)
+
+        def frame(seed):
+            p = rtnw.RenderParams(NX, NY, args.spp, max_depth=depth, background=bg, seed=seed, chunk=1,
+                                  sample_offset=k * args.spp)
+            return sc.render_tile_moments(cam, p, 0, 0, NX, NY) + (sc.render_features(cam, p, 0, 0, NX, NY),)
+        color, mom, f = frame(args.seed)
+        pr = rtnw.RenderParams(NX, NY, args.ref_spp, max_depth=depth, background=bg, seed=args.seed + 977)
+        ref = sc.render_tile(cam, pr, 0, 0, NX, NY)
+        row = dict(frame=k, raw=gamma_rms(color, ref), error={}, clipped={})
+        for s in settings:
+            h, r, g = s
+            c, m, ln, clip = rtnw.temporal_clamped(color, f, mom, args.spp, cam, hist[s], prev_cam, max_history=h, radius=r,
+                                                   gamma=g)
+            row["error"][key(s)] = gamma_rms(c, ref)
+            row["clipped"][key(s)] = float((clip != 0).sum() / max(1, (ln > args.spp).sum()))
+            hist[s] = dict(color=c, moments=m, len=ln, features=f)
+        # the yardstick once more, on other samples of the same frames
+        color2, mom2, f2 = frame(args.seed + 1)
+        c, m, ln = rtnw.temporal(color2, f2, mom2, args.spp, cam, repeat_hist, prev_cam, max_history=YARDSTICK)
+        row["repeat"] = gamma_rms(c, ref)
+        repeat_hist = dict(color=c, moments=m, len=ln, features=f2)
+        prev_cam = cam
+        rows.append(row)
+        best = min(row["error"], key=row["error"].get)
+        print(f"{scene} frame {k}: raw {row['raw']:.4f} " +
+              " ".join(f"[{h} unclamped {row['error'][key((h, 0, 0.0))]:.4f}]" for h in args.max_history) +
+              f" repeat {row['repeat']:.4f} best {best} {row['error'][best]:.4f}", flush=True)
+    # cost, on this scene's last two frames: a reprojected call of rt_temporal itself, then of the clamped entry
+    # point at every radius (with the mask, which its kernel writes)
+    last = hist[(YARDSTICK, 0, 0.0)]
+    before = camera(scene, args.frames - 2)
+    times = {}
+    for r in [0] + list(args.radius):
+        call = (lambda: rtnw.temporal(color, f, mom, args.spp, cam, last, before, timing=True)[3]) if r == 0 else \
+               (lambda: rtnw.temporal_clamped(color, f, mom, args.spp, cam, last, before, radius=r, gamma=1.0, timing=True)[4])
+        ms = [call() for _ in range(args.reps + 3)][3:]
+        times["rt_temporal" if r == 0 else f"radius {r}"] = dict(median_ms=statistics.median(ms), min_ms=min(ms), max_ms=max(ms))
+    sc.close()
+    return dict(scene=scene, frames=rows, kernel_ms=times)
+
+
+YARDSTICK = 16   # the unclamped max_history every setting is held against (TEMPORAL_DEFAULTS')
+
+
+def key(s):
+    h, r, g = s
+    return f"{h} unclamped" if r == 0 else f"{h} r{r} g{g:g}"
+
+
+def clamp_main(args):
+    if YARDSTICK not in args.max_history:
+        args.max_history = [YARDSTICK] + args.max_history
+    res = dict(nx=NX, ny=NY, frames=args.frames, spp=args.spp, ref_spp=args.ref_spp, max_history=args.max_history,
+               radius=args.radius, gamma=args.gamma,
+               settings={k: rtnw.TEMPORAL_DEFAULTS[k] for k in ("cos_normal", "sigma_depth")},
+               scenes=[clamp_scene(s, args) for s in args.scenes])
+    clamp_report(res, args.out)
+
+
+def clamp_report(res, out):
+    """The table (.md) and its numbers (.json: per setting the mean over the second half of the
+    frames, the last frame's error and the clipped share; per frame only the raw, the unclamped
+    and the tightest box's series, which show the drift)."""
+    os.makedirs(out, exist_ok=True)
+    hs, rs, gs, nf = res["max_history"], res["radius"], res["gamma"], res["frames"]
+    tail = range(nf // 2, nf)
+    md = [f"# tools/temporal_probe.py --clamp: {NX}x{NY}, {nf} frames of {res['spp']} spp, gamma RMS of the accumulated "
+          f"frame against {res['ref_spp']} spp of the same frame with another seed, mean over frames {tail[0]}-{tail[-1]} "
+          f"(and the last frame's); cos_normal {res['settings']['cos_normal']}, sigma_depth {res['settings']['sigma_depth']}", ""]
+    scenes = []
+    for s in res["scenes"]:
+        rows = s["frames"]
+        mean = lambda get: sum(get(rows[k]) for k in tail) / len(tail)
+        tail_mean = {n: mean(lambda r: r["error"][n]) for n in rows[0]["error"]}
+        tail_clipped = {n: mean(lambda r: r["clipped"][n]) for n in rows[0]["clipped"]}
+        repeat, yard = mean(lambda r: r["repeat"]), key((YARDSTICK, 0, 0.0))
+        spread = abs(repeat - tail_mean[yard])
+        per_frame = [abs(rows[k]["repeat"] - rows[k]["error"][yard]) for k in tail]   # the two runs, frame by frame
+        best = min(tail_mean, key=tail_mean.get)
+        md += [f"## {s['scene']}", "",
+               f"raw {mean(lambda r: r['raw']):.4f}; unclamped max_history {YARDSTICK}: {tail_mean[yard]:.4f}, on "
+               f"other samples {repeat:.4f} (the means differ by {spread:.6f}; frame by frame the two runs differ by "
+               f"{sum(per_frame) / len(per_frame):.5f} in the mean and {max(per_frame):.5f} at the most); lowest: {best} "
+               f"{tail_mean[best]:.4f}", "",
+               "mean error (last frame's error; share of the pixels with history that the clamp moved)", "",
+               "| max_history | unclamped | radius | " + " | ".join(f"gamma {g:g}" for g in gs) + " |",
+               "|---|---|---|" + "---|" * len(gs)]
+        for h in hs:
+            for r in rs:
+                u = key((h, 0, 0.0))
+                md.append(f"| {h} | {tail_mean[u]:.4f} ({rows[-1]['error'][u]:.4f}) | {r} | " + " | ".join(
+                    f"{tail_mean[n]:.4f} ({rows[-1]['error'][n]:.4f}; {tail_clipped[n]:.2f})"
+                    for n in (key((h, r, g)) for g in gs)) + " |")
+        md += ["", "| reprojected call | kernel ms (median, min-max) |", "|---|---|"]
+        for name, t in s["kernel_ms"].items():
+            md.append(f"| {name} | {t['median_ms']:.4f} ({t['min_ms']:.4f}-{t['max_ms']:.4f}) |")
+        md.append("")
+        shown = [key((h, 0, 0.0)) for h in hs] + [key((h, rs[0], gs[0])) for h in hs]
+        series = {n: [round(r["error"][n], 5) for r in rows] for n in shown}
+        series.update(raw=[round(r["raw"], 5) for r in rows], repeat=[round(r["repeat"], 5) for r in rows])
+        scenes.append(dict(scene=s["scene"], yardstick=round(tail_mean[yard], 6), repeat=round(repeat, 6),
+                           spread=round(spread, 6), per_frame_spread_mean=round(sum(per_frame) / len(per_frame), 6),
+                           per_frame_spread_max=round(max(per_frame), 6), lowest=best,
+                           kernel_ms={n: [round(t[k], 5) for k in ("median_ms", "min_ms", "max_ms")]
+                                      for n, t in s["kernel_ms"].items()},
+                           mean_last_clipped={n: [round(tail_mean[n], 5), round(rows[-1]["error"][n], 5),
+                                                  round(tail_clipped[n], 3)] for n in tail_mean},
+                           per_frame=series))
+    small = dict({k: v for k, v in res.items() if k != "scenes"}, tail=[tail[0], tail[-1]], scenes=scenes)
+    text = re.sub(r"\[[^\[\]{}]*\]", lambda m: re.sub(r"\s+", " ", m.group(0)), json.dumps(small, indent=1))   # a list a line
+    with open(os.path.join(out, "temporal_clamp_probe.json"), "w") as fh:
+        fh.write(text + "\n")
+    with open(os.path.join(out, "temporal_clamp_probe.md"), "w") as fh:
+        fh.write("\n".join(md))
+    print("\n".join(md))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default="temporal_probe_out")
@@ -103,7 +241,12 @@ def main():
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--max-history", type=int, nargs="+", default=[4, 8, 16, 32, 64, 128])
+    ap.add_argument("--clamp", action="store_true", help="measure rt_temporal_clamped instead (see above)")
+    ap.add_argument("--radius", type=int, nargs="+", default=[1, 2, 3])
+    ap.add_argument("--gamma", type=float, nargs="+", default=[0.5, 1.0, 1.5, 2.0, 3.0])
     args = ap.parse_args()
+    if args.clamp:
+        return clamp_main(args)
     os.makedirs(args.out, exist_ok=True)
     res = dict(nx=NX, ny=NY, frames=args.frames, spp=args.spp, ref_spp=args.ref_spp, max_history=args.max_history,
                settings={k: rtnw.TEMPORAL_DEFAULTS[k] for k in ("cos_normal", "sigma_depth")},
