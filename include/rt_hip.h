@@ -586,6 +586,65 @@ int rt_temporal_clamped_dev(int device, int nx, int ny, const rt_temporal_frame 
                             const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped_dev,
                             void *stream);
 
+/* ------------------------------- the same with a history for background and edge pixels */
+enum { RT_TEMPORAL_SRC_NONE = 0, RT_TEMPORAL_SRC_SURFACE = 1, RT_TEMPORAL_SRC_BACKGROUND = 2,
+       RT_TEMPORAL_SRC_EDGE = 4 /* or'ed in: 0 < coverage < 1 */, RT_TEMPORAL_SRC_SAME = 8 /* equal cameras */ };
+typedef struct rt_temporal_cover_params {   /* 32 bytes */
+    int32_t background;      /* 0 / 1: pixels that miss take history by direction */
+    int32_t edges;           /* 0 / 1: partly covered pixels take the class of their dominant part */
+    float   sigma_coverage;  /* >= 0, finite: a tap counts only when |c - c_q| <= sigma_coverage */
+    int32_t pad[5];          /* zero */
+} rt_temporal_cover_params;
+/* rt_temporal_clamped with a history for the pixels rt_temporal gives none under unequal cameras:
+ * those that look past the geometry and those on a silhouette.  Every argument of
+ * rt_temporal_clamped means what it means there (cp is required; radius 0 means no clamp).  With
+ * c the pixel's coverage, a pixel belongs to one of two classes or to none:
+ *   surf = c == 1 || (edges && c >= 0.5);
+ *   back = !surf && background && (c == 0 || (edges && c < 0.5));
+ *   neither: no history, the output is the frame bit for bit.
+ * A surface pixel's guides are means over samples in which a miss contributes 0, so the hit
+ * samples' means are n = normal / c and z = depth / c (IEEE divides; the same bits for c == 1); it
+ * is reprojected as rt_temporal does with z as its depth.  A background pixel is a point at
+ * infinity: d = dir, the direction through the pixel centre, with no expected depth.  From
+ * d . w' < 0 to the four taps and their weights both classes follow rt_temporal's rule.  A tap q
+ * with coverage c_q counts when its weight is positive, it is inside the image, hist len[q] > 0,
+ * |c - c_q| <= sigma_coverage and
+ *   for a surface pixel: c_q == 1 || (edges && c_q >= 0.5), n . (n_q / c_q) >= cos_normal, and
+ *     rt_temporal's depth test on z' = |d| and z_q = depth_q / c_q;
+ *   for a background pixel: c_q == 0 || (edges && c_q < 0.5), and nothing else.
+ * W, the history colour, the per-sample moments and n_h are formed as in rt_temporal; with
+ * cp->radius >= 1 rt_temporal_clamped's clamp runs on every pixel that found a history, whatever
+ * its class; the blend is rt_temporal's.  `source` (nx*ny, or NULL) receives per pixel where its
+ * history came from: RT_TEMPORAL_SRC_NONE without one, else RT_TEMPORAL_SRC_SURFACE or
+ * RT_TEMPORAL_SRC_BACKGROUND, with RT_TEMPORAL_SRC_EDGE or'ed in when c is neither 0 nor 1.
+ * With vp zeroed (background 0, edges 0, any valid sigma_coverage) this is rt_temporal_clamped bit
+ * for bit and source is 1 exactly where a history was used: coverage 1 against coverage 1 passes
+ * every new test, so the settings only add pixels and taps.  A first frame is rt_temporal bit for
+ * bit with clipped 0 and source 0; so are bytewise equal cameras, with clipped 0 and source
+ * RT_TEMPORAL_SRC_SAME where a history was used.  The exact float32 statement is
+ * tests/test_temporal_cover_spec.py (temporal_cover_ref).
+ * Suggested: background 1, edges 1, sigma_coverage 0.5, no clamp (DESIGN.md §7k records the sweep:
+ * over a camera move at 4 spp a frame that lowers final()'s error by 28 %, 98 % of its pixels
+ * taking a history instead of 41 %, and random_scene's by 1.4 %; 3 us on rt_temporal's 25 us).
+ * Host form: as rt_temporal_clamped's; `source` is a host pointer; *ms is the kernel's time (a
+ * first frame's and equal cameras' mask and source are written ahead of the timed interval).
+ * RT_ERR_INVALID: every case of rt_temporal_clamped, with its message; then, checked before the
+ * device is touched and named in rt_last_error(), a null vp, background or edges other than 0 or
+ * 1, sigma_coverage negative, NaN or infinite, a nonzero pad; `source` equal to `clipped` or to one
+ * of the arrays of cur, hist or out. */
+int rt_temporal_cover(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                      const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                      const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp, const rt_temporal_frame *out,
+                      int32_t *clipped, int32_t *source, double *ms);
+/* The same with device pointers in the frames and for clipped_dev and source_dev (each may be
+ * NULL), enqueued on `stream`; a first frame's and equal cameras' mask and source are written on
+ * `stream` ahead of the kernel.  No workspace: calls may overlap; the history sets ping-pong as
+ * rt_temporal_dev's. */
+int rt_temporal_cover_dev(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                          const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                          const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp,
+                          const rt_temporal_frame *out, int32_t *clipped_dev, int32_t *source_dev, void *stream);
+
 /* ------------------------------- ray queries on the caller's own rays */
 #define RT_HIT_MISS (-1)
 #define RT_HIT_INVALID (-2)

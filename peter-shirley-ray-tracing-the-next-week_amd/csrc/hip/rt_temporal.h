@@ -40,10 +40,29 @@ extern "C" hipError_t rt_launch_temporal_clamped(int nx, int ny, int mode, const
                                                  const rt_temporal_clamp_params *cp, const rt_temporal_frame *out,
                                                  int32_t *clipped, hipStream_t stream);
 
+// rt_launch_temporal_clamped with a history for background and edge pixels (rt_temporal_cover;
+// DESIGN.md §7k).  Mode RT_TEMPORAL_REPROJECT runs the cover kernel at any radius in 0..3, which
+// writes `clipped` and `source` (device, nx * ny each, or null; buffers of their own) itself;
+// every other mode runs rt_launch_temporal's and leaves both alone: the caller fills them then,
+// outside what it times (zeros, and under equal cameras rt_launch_temporal_same for `source`).
+// cp and vp have passed capi_temporal.cpp's checks.
+extern "C" hipError_t rt_launch_temporal_cover(int nx, int ny, int mode, const rt_temporal_frame *cur,
+                                               const rt_camera_desc *cam, const rt_temporal_frame *hist,
+                                               const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                                               const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp,
+                                               const rt_temporal_frame *out, int32_t *clipped, int32_t *source,
+                                               hipStream_t stream);
+// source[p] = RT_TEMPORAL_SRC_SAME where mode RT_TEMPORAL_STATIC uses the history of pixel p
+// (min(hist_len[p], max_history) > 0), else 0.
+extern "C" hipError_t rt_launch_temporal_same(int nx, int ny, const int32_t *hist_len, int max_history, int32_t *source,
+                                              hipStream_t stream);
+
 // capi_temporal.cpp reaches the launchers through this table, filled by rt_temporal.hip's static
 // initialiser when the unit is linked in (like rt_firefly.h's RtFireflyLaunch).
 struct RtTemporalLaunch {
     decltype(&rt_launch_temporal) accumulate;
     decltype(&rt_launch_temporal_clamped) accumulate_clamped;
+    decltype(&rt_launch_temporal_cover) accumulate_cover;
+    decltype(&rt_launch_temporal_same) mark_same;
 };
 extern "C" RtTemporalLaunch rt_temporal_launch;   // defined (empty) in capi_temporal.cpp

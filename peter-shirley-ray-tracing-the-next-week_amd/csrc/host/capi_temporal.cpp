@@ -1,6 +1,7 @@
 // capi_temporal.cpp — the reprojected frame history that runs ahead of the denoiser
 // (rt_temporal.hip; rt_hip.h): the argument checks, rt_temporal_dev and the host
-// form, and the same two over the clamped launcher (rt_temporal_clamped).
+// form, the same two over the clamped launcher (rt_temporal_clamped) and over the one that also
+// serves background and edge pixels (rt_temporal_cover).
 #include <cmath>
 #include <cstring>
 
@@ -9,7 +10,7 @@
 #include "../hip/rt_temporal.h"
 
 // the unit's launcher, set by its static initialiser (rt_temporal.h)
-RtTemporalLaunch rt_temporal_launch = {nullptr, nullptr};
+RtTemporalLaunch rt_temporal_launch = {nullptr, nullptr, nullptr, nullptr};
 
 // All before any HIP call, the parameter named in the message.
 static int temporal_check(const char *fn, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
@@ -75,17 +76,56 @@ static int temporal_clamp_check(const char *fn, int nx, int ny, const rt_tempora
     return RT_OK;
 }
 
+// rt_temporal_cover's checks: rt_temporal_clamped's, then the cover's own.
+static int temporal_cover_check(const char *fn, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                                const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                                const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp,
+                                const rt_temporal_frame *out, const int32_t *clipped, const int32_t *source) {
+    if (int rc = temporal_clamp_check(fn, nx, ny, cur, cam, hist, prev_cam, tp, cp, out, clipped)) return rc;
+    const std::string f(fn);
+    if (!vp) return fail(RT_ERR_INVALID, f + ": null argument (vp)");
+    if (vp->background != 0 && vp->background != 1) return fail(RT_ERR_INVALID, f + ": background must be 0 or 1");
+    if (vp->edges != 0 && vp->edges != 1) return fail(RT_ERR_INVALID, f + ": edges must be 0 or 1");
+    if (!(vp->sigma_coverage >= 0.0f) || std::isinf(vp->sigma_coverage))
+        return fail(RT_ERR_INVALID, f + ": sigma_coverage must not be negative, NaN or infinite");
+    for (int32_t w : vp->pad)
+        if (w) return fail(RT_ERR_INVALID, f + ": pad of the cover's parameters must be zero");
+    if (source) {   // written like `clipped`: a buffer of its own
+        const void *c = source;
+        if (c == clipped) return fail(RT_ERR_INVALID, f + ": source must not be clipped");
+        const rt_temporal_frame none = {nullptr, nullptr, nullptr, nullptr};
+        for (const rt_temporal_frame *fr : {cur, hist ? hist : &none, out})
+            if (c == fr->color || c == fr->guides || c == fr->moments || c == fr->len)
+                return fail(RT_ERR_INVALID, f + ": source must not be one of the frames' arrays");
+    }
+    if (!rt_temporal_launch.accumulate_cover || !rt_temporal_launch.mark_same) return unit_missing(f, "temporal", "rt_temporal.o");
+    return RT_OK;
+}
+
 // Bytewise equal cameras: a pixel's history is its own pixel (rt_hip.h).
 static int temporal_mode(const rt_temporal_frame *hist, const rt_camera_desc *cam, const rt_camera_desc *prev_cam) {
     if (!hist) return RT_TEMPORAL_FIRST;
     return std::memcmp(cam, prev_cam, sizeof(rt_camera_desc)) == 0 ? RT_TEMPORAL_STATIC : RT_TEMPORAL_REPROJECT;
 }
 
-// The host form of both entry points, the checks made: every array staged in one allocation, the
-// kernel timed alone.  `cp` null is rt_temporal; with it, `clipped` (or null) is staged back too.
+// rt_temporal_cover where rt_temporal's kernel runs (a first frame, equal cameras): no channel is
+// clipped, and a history comes from the pixel itself or from nowhere.  Device pointers, on `stream`.
+static int temporal_cover_fill(int nx, int ny, int mode, const int32_t *hist_len, const rt_temporal_params *tp, int32_t *clipped,
+                               int32_t *source, hipStream_t stream) {
+    const size_t bytes = (size_t)nx * ny * sizeof(int32_t);
+    if (clipped) HIP_TRY(hipMemsetAsync(clipped, 0, bytes, stream));
+    if (source && mode == RT_TEMPORAL_FIRST) HIP_TRY(hipMemsetAsync(source, 0, bytes, stream));
+    if (source && mode == RT_TEMPORAL_STATIC) HIP_TRY(rt_temporal_launch.mark_same(nx, ny, hist_len, tp->max_history, source, stream));
+    return RT_OK;
+}
+
+// The host form of the entry points, the checks made: every array staged in one allocation, the
+// kernel timed alone.  `cp` null is rt_temporal; with it, `clipped` (or null) is staged back too;
+// with `vp` besides it is rt_temporal_cover, and so is `source` (or null).
 static int temporal_host(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
                          const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
-                         const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped, double *ms) {
+                         const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp, const rt_temporal_frame *out,
+                         int32_t *clipped, int32_t *source, double *ms) {
     HIP_TRY(hipSetDevice(device));
     const size_t npix = (size_t)nx * ny;
     // in floats (an int32 count takes a float's room); the guides first: 16-B loads
@@ -93,7 +133,7 @@ static int temporal_host(int device, int nx, int ny, const rt_temporal_frame *cu
     Staging st;
     const auto cur_g = st.floats(g), hist_g = st.floats(g), cur_c = st.floats(c), hist_c = st.floats(c), out_c = st.floats(c),
                cur_m = st.floats(m), hist_m = st.floats(m), out_m = st.floats(m), hist_l = st.floats(l), out_l = st.floats(l),
-               clip = st.floats(clipped ? l : 0);
+               clip = st.floats(clipped ? l : 0), src = st.floats(source ? l : 0);
     RT_TRY(st.reserve());
     RT_TRY(st.upload(cur_g, cur->guides));
     RT_TRY(st.upload(cur_c, cur->color));
@@ -109,10 +149,17 @@ static int temporal_host(int device, int nx, int ny, const rt_temporal_frame *cu
                                      (const int32_t *)st.ptr(hist_l)};
     const rt_temporal_frame dout = {st.ptr(out_c), nullptr, st.ptr_if(out->moments, out_m), (const int32_t *)st.ptr(out_l)};
     const int mode = temporal_mode(hist, cam, prev_cam);
-    if (cp && clipped && !rt_temporal_clamps(mode, cp))   // rt_temporal's kernel runs: no channel is clipped
+    if (vp && mode != RT_TEMPORAL_REPROJECT)
+        RT_TRY(temporal_cover_fill(nx, ny, mode, dhist.len, tp, (int32_t *)st.ptr_if(clipped, clip),
+                                   (int32_t *)st.ptr_if(source, src), nullptr));
+    else if (!vp && cp && clipped && !rt_temporal_clamps(mode, cp))   // rt_temporal's kernel runs: no channel is clipped
         HIP_TRY(hipMemsetAsync(st.ptr(clip), 0, npix * sizeof(int32_t), nullptr));
     RT_TRY(st.begin());   // the events bracket the kernel alone
-    if (cp)
+    if (vp)
+        HIP_TRY(rt_temporal_launch.accumulate_cover(nx, ny, mode, &dcur, cam, hist ? &dhist : nullptr, prev_cam, tp, cp, vp, &dout,
+                                                    (int32_t *)st.ptr_if(clipped, clip), (int32_t *)st.ptr_if(source, src),
+                                                    nullptr));
+    else if (cp)
         HIP_TRY(rt_temporal_launch.accumulate_clamped(nx, ny, mode, &dcur, cam, hist ? &dhist : nullptr, prev_cam, tp, cp, &dout,
                                                       (int32_t *)st.ptr_if(clipped, clip), nullptr));
     else
@@ -123,6 +170,7 @@ static int temporal_host(int device, int nx, int ny, const rt_temporal_frame *cu
     RT_TRY(st.download((float *)out->moments, out_m));
     RT_TRY(st.download((int32_t *)out->len, out_l));
     RT_TRY(st.download(clipped, clip));
+    RT_TRY(st.download(source, src));
     return st.elapsed(ms);
 }
 
@@ -142,7 +190,7 @@ int rt_temporal(int device, int nx, int ny, const rt_temporal_frame *cur, const 
                 const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
                 const rt_temporal_frame *out, double *ms) {
     if (int rc = temporal_check("rt_temporal", nx, ny, cur, cam, hist, prev_cam, tp, out)) return rc;
-    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, nullptr, out, nullptr, ms);
+    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, nullptr, nullptr, out, nullptr, nullptr, ms);
 }
 
 int rt_temporal_clamped_dev(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
@@ -163,7 +211,32 @@ int rt_temporal_clamped(int device, int nx, int ny, const rt_temporal_frame *cur
                         const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
                         const rt_temporal_clamp_params *cp, const rt_temporal_frame *out, int32_t *clipped, double *ms) {
     if (int rc = temporal_clamp_check("rt_temporal_clamped", nx, ny, cur, cam, hist, prev_cam, tp, cp, out, clipped)) return rc;
-    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, cp, out, clipped, ms);
+    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, cp, nullptr, out, clipped, nullptr, ms);
+}
+
+int rt_temporal_cover_dev(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                          const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                          const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp,
+                          const rt_temporal_frame *out, int32_t *clipped_dev, int32_t *source_dev, void *stream) {
+    if (int rc = temporal_cover_check("rt_temporal_cover_dev", nx, ny, cur, cam, hist, prev_cam, tp, cp, vp, out, clipped_dev,
+                                      source_dev))
+        return rc;
+    HIP_TRY(hipSetDevice(device));
+    const int mode = temporal_mode(hist, cam, prev_cam);
+    if (mode != RT_TEMPORAL_REPROJECT)
+        RT_TRY(temporal_cover_fill(nx, ny, mode, hist ? hist->len : nullptr, tp, clipped_dev, source_dev, (hipStream_t)stream));
+    HIP_TRY(rt_temporal_launch.accumulate_cover(nx, ny, mode, cur, cam, hist, prev_cam, tp, cp, vp, out, clipped_dev, source_dev,
+                                                (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_temporal_cover(int device, int nx, int ny, const rt_temporal_frame *cur, const rt_camera_desc *cam,
+                      const rt_temporal_frame *hist, const rt_camera_desc *prev_cam, const rt_temporal_params *tp,
+                      const rt_temporal_clamp_params *cp, const rt_temporal_cover_params *vp, const rt_temporal_frame *out,
+                      int32_t *clipped, int32_t *source, double *ms) {
+    if (int rc = temporal_cover_check("rt_temporal_cover", nx, ny, cur, cam, hist, prev_cam, tp, cp, vp, out, clipped, source))
+        return rc;
+    return temporal_host(device, nx, ny, cur, cam, hist, prev_cam, tp, cp, vp, out, clipped, source, ms);
 }
 
 }  // extern "C"

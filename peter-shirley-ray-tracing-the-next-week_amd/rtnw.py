@@ -167,6 +167,20 @@ class RtTemporalClampParams(ctypes.Structure):   # 32 bytes
 TEMPORAL_CLAMP_DEFAULTS = dict(max_history=16, radius=0, gamma=1.0)
 
 
+class RtTemporalCoverParams(ctypes.Structure):   # 32 bytes
+    _fields_ = [("background", ctypes.c_int32), ("edges", ctypes.c_int32), ("sigma_coverage", ctypes.c_float),
+                ("pad", ctypes.c_int32 * 5)]
+
+
+# where rt_temporal_cover's history came from, per pixel (rt_hip.h)
+RT_TEMPORAL_SRC_NONE, RT_TEMPORAL_SRC_SURFACE, RT_TEMPORAL_SRC_BACKGROUND, RT_TEMPORAL_SRC_EDGE, RT_TEMPORAL_SRC_SAME = 0, 1, 2, 4, 8
+
+# rt_temporal_cover's settings when none are given.  DESIGN.md §7k records the sweep: background and edges with
+# sigma_coverage 0.5 lower the error on both scenes (final() 0.169 -> 0.122, random_scene 0.0345 -> 0.0340), so they
+# are on; the clamp still costs final() more than it gains random_scene, so radius stays 0
+TEMPORAL_COVER_DEFAULTS = dict(max_history=16, radius=0, gamma=1.0, background=1, edges=1, sigma_coverage=0.5)
+
+
 class RtRay(ctypes.Structure):   # 48 bytes
     _fields_ = [("origin", ctypes.c_float * 3), ("t_min", ctypes.c_float), ("dir", ctypes.c_float * 3),
                 ("t_max", ctypes.c_float), ("time", ctypes.c_float), ("pad", ctypes.c_float * 3)]
@@ -350,7 +364,16 @@ def lib():
                                                        P(RtCameraDesc), P(RtTemporalFrame), P(RtCameraDesc),
                                                        P(RtTemporalParams), P(RtTemporalClampParams), P(RtTemporalFrame),
                                                        ctypes.c_void_p, ctypes.c_void_p]),
-            "rt_trace_rays": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+            "rt_temporal_cover": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame),
+                                                 P(RtCameraDesc), P(RtTemporalFrame), P(RtCameraDesc), P(RtTemporalParams),
+                                                 P(RtTemporalClampParams), P(RtTemporalCoverParams), P(RtTemporalFrame),
+                                                 ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_double)]),
+            "rt_temporal_cover_dev": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(RtTemporalFrame),
+                                                     P(RtCameraDesc), P(RtTemporalFrame), P(RtCameraDesc),
+                                                     P(RtTemporalParams), P(RtTemporalClampParams),
+                                                     P(RtTemporalCoverParams), P(RtTemporalFrame), ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p]),
+            "rt_trace_rays":(ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                              P(ctypes.c_double)]),
             "rt_trace_rays_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
@@ -405,13 +428,13 @@ def lib():
             "rt_version": (ctypes.c_char_p, []),
         }
         # what a library built before them lacks (A/B variants): diagnostics, the moments and adaptive entries,
-        # the feature pass, the denoiser, the firefly clamp, the frame history and its clamped form, the ray
-        # queries, the radiance queries and the lens renders
+        # the feature pass, the denoiser, the firefly clamp, the frame history, its clamped form and the one for
+        # background and edge pixels, the ray queries, the radiance queries and the lens renders
         optional = {"rt_math_probe", "rt_render_tiles_moments", "rt_render_adaptive", "rt_render_adaptive_guarded",
                     "rt_copy_to_device", "rt_lens_rays", "rt_lens_rays_dev", "rt_render_lens", "rt_render_lens_dev",
                     "rt_render_features", "rt_render_features_dev", "rt_denoise", "rt_denoise_dev",
                     "rt_firefly", "rt_firefly_dev", "rt_temporal", "rt_temporal_dev",
-                    "rt_temporal_clamped", "rt_temporal_clamped_dev", "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
+                    "rt_temporal_clamped", "rt_temporal_clamped_dev", "rt_temporal_cover", "rt_temporal_cover_dev", "rt_trace_rays", "rt_trace_rays_dev", "rt_occluded", "rt_occluded_dev",
                     "rt_radiance_rays", "rt_radiance_rays_dev"}
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
@@ -895,9 +918,14 @@ def temporal_clamp_params(radius=None, gamma=None):
     return _params(RtTemporalClampParams, TEMPORAL_CLAMP_DEFAULTS, ("radius",), dict(radius=radius, gamma=gamma))
 
 
-def _temporal(color, features, moments, cam, history, prev_cam, tp, cp, device):
-    """rt_temporal (cp None) or rt_temporal_clamped on host arrays: (color, moments or None, len,
-    clipped or None, the kernel's ms)."""
+def temporal_cover_params(background=None, edges=None, sigma_coverage=None):
+    given = dict(background=background, edges=edges, sigma_coverage=sigma_coverage)
+    return _params(RtTemporalCoverParams, TEMPORAL_COVER_DEFAULTS, ("background", "edges"), given)
+
+
+def _temporal(color, features, moments, cam, history, prev_cam, tp, cp, device, vp=None):
+    """rt_temporal (cp None), rt_temporal_clamped or (with vp) rt_temporal_cover on host arrays:
+    (color, moments or None, len, clipped or None, the kernel's ms), and source after them with vp."""
     c = np.ascontiguousarray(color, np.float32)
     ny, nx, _ = c.shape
     g = pack_guides(features).reshape(ny, nx, 8)
@@ -921,6 +949,11 @@ def _temporal(color, features, moments, cam, history, prev_cam, tp, cp, device):
     clipped = None
     if cp is None:
         _check(lib().rt_temporal(*head, ctypes.byref(dst), ctypes.byref(ms)))
+    elif vp is not None:
+        clipped, source = np.zeros((ny, nx), np.int32), np.zeros((ny, nx), np.int32)
+        _check(lib().rt_temporal_cover(*head, ctypes.byref(cp), ctypes.byref(vp), ctypes.byref(dst), clipped.ctypes.data,
+                                       source.ctypes.data, ctypes.byref(ms)))
+        return out, om, ol, clipped, ms.value, source
     else:
         clipped = np.zeros((ny, nx), np.int32)
         _check(lib().rt_temporal_clamped(*head, ctypes.byref(cp), ctypes.byref(dst), clipped.ctypes.data, ctypes.byref(ms)))
@@ -956,6 +989,26 @@ def temporal_clamped(color, features, moments, frame_spp, cam: Camera, history=N
                          cos_normal, sigma_depth)
     res = _temporal(color, features, moments, cam, history, prev_cam, tp, temporal_clamp_params(radius, gamma), device)
     return res if timing else res[:4]
+
+
+def temporal_cover(color, features, moments, frame_spp, cam: Camera, history=None, prev_cam: Camera | None = None, *,
+                   background=None, edges=None, sigma_coverage=None, radius=None, gamma=None, max_history=None,
+                   cos_normal=None, sigma_depth=None, device: int = 0, timing: bool = False):
+    """`temporal_clamped` with a history for the pixels it gives none under a moving camera
+    (rt_temporal_cover): with `background` 1 a pixel that misses the geometry takes its history
+    by direction, with `edges` 1 a partly covered pixel takes the class of its dominant part
+    (surface from coverage 0.5 on), and a tap counts only when its coverage is within
+    `sigma_coverage` of the pixel's.  Unset settings take TEMPORAL_COVER_DEFAULTS, cos_normal and
+    sigma_depth TEMPORAL_DEFAULTS.  Returns (color, moments or None, len, clipped, source): source
+    [ny, nx] int32 says where a pixel's history came from (RT_TEMPORAL_SRC_*: 0 none, 1 surface,
+    2 background, 4 or'ed in on a partly covered pixel, 8 its own pixel under equal cameras) (and
+    the kernel's ms after them with timing=True)."""
+    d = TEMPORAL_COVER_DEFAULTS
+    tp = temporal_params(frame_spp, d["max_history"] if max_history is None else max_history, cos_normal, sigma_depth)
+    cp = temporal_clamp_params(d["radius"] if radius is None else radius, d["gamma"] if gamma is None else gamma)
+    out, om, ol, clipped, ms, source = _temporal(color, features, moments, cam, history, prev_cam, tp, cp, device,
+                                                 temporal_cover_params(background, edges, sigma_coverage))
+    return (out, om, ol, clipped, source, ms) if timing else (out, om, ol, clipped, source)
 
 
 # ------------------------------------------------------------ multi-GPU (RCCL)

@@ -33,6 +33,15 @@ anything; and the kernel's time for a reprojected frame, rt_temporal's and the c
 point's at radius 1, 2 and 3.  Writes
 <out>/temporal_clamp_probe.md and .json (the table's numbers; per frame only the unclamped and
 the tightest box's series).
+
+--cover measures rt_temporal_cover over the same camera moves at max_history 16:
+plain (rt_temporal's rule), background only, and background and edges at every sigma_coverage of
+--sigma-coverage, each without a clamp and with the --cover-clamp one (radius 1, gamma 0.5), each
+setting carrying its own history: the gamma RMS of the accumulated image, the share of the pixels
+per `source` value and the share of the histories the clamp moved; rt_temporal once more on frames
+drawn with another seed, for the spread; and the kernel's time for a reprojected frame, rt_temporal's
+and rt_temporal_clamped's own kernels beside the cover kernel's with nothing and with everything on.
+Writes <out>/temporal_cover_probe.md and .json.
 """
 import argparse
 import json
@@ -231,6 +240,139 @@ def clamp_report(res, out):
     print("\n".join(md))
 
 
+def cover_settings(args):
+    """(background, edges, sigma_coverage, radius, gamma): plain, background only, background and
+    edges at every --sigma-coverage; each without a clamp and with the --cover-clamp one."""
+    classes = [(0, 0, 0.0), (1, 0, 0.0)] + [(1, 1, s) for s in args.sigma_coverage]
+    return [c + k for k in ((0, 0.0), tuple(args.cover_clamp)) for c in classes]
+
+
+def cover_key(s):
+    b, e, sg, r, g = s
+    name = "plain" if not b and not e else "background" if not e else f"background+edges s{sg:g}"
+    return name + (f", r{r} g{g:g}" if r else "")
+
+
+def cover_scene(scene, args):
+    _, bg, depth = rtnw.SCENE_DEFAULTS[scene]
+    sc = rtnw.Scene.builtin(scene)
+    settings = cover_settings(args)
+    hist = {s: None for s in settings}
+    repeat_hist, prev_cam, rows = None, None, []
+    for k in range(args.frames):
+        cam = camera(scene, k)
+
+        def frame(seed):
+            p = rtnw.RenderParams(NX, NY, args.spp, max_depth=depth, background=bg, seed=seed, chunk=1,
+                                  sample_offset=k * args.spp)
+            return sc.render_tile_moments(cam, p, 0, 0, NX, NY) + (sc.render_features(cam, p, 0, 0, NX, NY),)
+        color, mom, f = frame(args.seed)
+        pr = rtnw.RenderParams(NX, NY, args.ref_spp, max_depth=depth, background=bg, seed=args.seed + 977)
+        ref = sc.render_tile(cam, pr, 0, 0, NX, NY)
+        cov = np.asarray(f["coverage"], np.float32).reshape(NY, NX)
+        row = dict(frame=k, raw=gamma_rms(color, ref), error={}, source={}, clipped={},
+                   coverage=[float((cov == 0).mean()), float(((cov > 0) & (cov < 1)).mean()), float((cov == 1).mean())])
+        for s in settings:
+            b, e, sg, r, g = s
+            c, m, ln, clip, src = rtnw.temporal_cover(color, f, mom, args.spp, cam, hist[s], prev_cam, max_history=YARDSTICK,
+                                                      background=b, edges=e, sigma_coverage=sg, radius=r, gamma=g)
+            row["error"][cover_key(s)] = gamma_rms(c, ref)
+            row["source"][cover_key(s)] = {str(v): float((src == v).mean()) for v in (0, 1, 2, 5, 6)}
+            row["clipped"][cover_key(s)] = float((clip != 0).sum() / max(1, (src != 0).sum()))
+            hist[s] = dict(color=c, moments=m, len=ln, features=f)
+        # the yardstick (rt_temporal itself) once more, on other samples of the same frames
+        color2, mom2, f2 = frame(args.seed + 1)
+        c, m, ln = rtnw.temporal(color2, f2, mom2, args.spp, cam, repeat_hist, prev_cam, max_history=YARDSTICK)
+        row["repeat"] = gamma_rms(c, ref)
+        repeat_hist = dict(color=c, moments=m, len=ln, features=f2)
+        prev_cam = cam
+        rows.append(row)
+        print(f"{scene} frame {k}: raw {row['raw']:.4f} repeat {row['repeat']:.4f} " +
+              " ".join(f"[{n}: {v:.4f}]" for n, v in row["error"].items()), flush=True)
+    # cost, on this scene's last two frames: a reprojected call of rt_temporal's and rt_temporal_clamped's own kernels,
+    # then of the cover kernel (mask and source written) with nothing on, and with everything on, at radius 0 and 1
+    last = hist[settings[0]]
+    before = camera(scene, args.frames - 2)
+    r1, g1 = args.cover_clamp
+    calls = {
+        "rt_temporal": lambda: rtnw.temporal(color, f, mom, args.spp, cam, last, before, timing=True)[3],
+        f"rt_temporal_clamped r{r1}": lambda: rtnw.temporal_clamped(color, f, mom, args.spp, cam, last, before, radius=r1, gamma=g1,
+                                                                   timing=True)[4],
+    }
+    for name, (b, e) in (("plain", (0, 0)), ("background+edges", (1, 1))):
+        for r in (0, r1):
+            calls[f"rt_temporal_cover {name} r{r}"] = \
+                lambda b=b, e=e, r=r: rtnw.temporal_cover(color, f, mom, args.spp, cam, last, before, background=b, edges=e,
+                                                          sigma_coverage=0.25, radius=r, gamma=g1, timing=True)[5]
+    times = {}
+    for name, call in calls.items():
+        ms = [call() for _ in range(args.reps + 3)][3:]
+        times[name] = dict(median_ms=statistics.median(ms), min_ms=min(ms), max_ms=max(ms))
+    sc.close()
+    return dict(scene=scene, frames=rows, kernel_ms=times)
+
+
+def cover_report(res, out):
+    """The table (.md) and its numbers (.json: per setting the mean over the second half of the
+    frames of the error, of the share of pixels per source value and of the clipped share; per
+    frame the raw, the repeat and every setting's error)."""
+    os.makedirs(out, exist_ok=True)
+    nf = res["frames"]
+    tail = range(nf // 2, nf)
+    md = [f"# tools/temporal_probe.py --cover: {NX}x{NY}, {nf} frames of {res['spp']} spp, gamma RMS of the accumulated frame "
+          f"against {res['ref_spp']} spp of the same frame with another seed, mean over frames {tail[0]}-{tail[-1]} (and the "
+          f"last frame's); max_history {YARDSTICK}, cos_normal {res['settings']['cos_normal']}, sigma_depth "
+          f"{res['settings']['sigma_depth']}; clamp: radius {res['cover_clamp'][0]:g}, gamma {res['cover_clamp'][1]:g}", ""]
+    scenes = []
+    for s in res["scenes"]:
+        rows = s["frames"]
+        mean = lambda get: sum(get(rows[k]) for k in tail) / len(tail)
+        names = list(rows[0]["error"])
+        err = {n: mean(lambda r: r["error"][n]) for n in names}
+        src = {n: {v: mean(lambda r: r["source"][n][v]) for v in rows[0]["source"][n]} for n in names}
+        clip = {n: mean(lambda r: r["clipped"][n]) for n in names}
+        covg = [mean(lambda r: r["coverage"][i]) for i in range(3)]
+        repeat = mean(lambda r: r["repeat"])
+        per_frame = [abs(rows[k]["repeat"] - rows[k]["error"]["plain"]) for k in tail]
+        md += [f"## {s['scene']}", "",
+               f"raw {mean(lambda r: r['raw']):.4f}; plain (rt_temporal's rule): {err['plain']:.4f}, rt_temporal on other samples "
+               f"{repeat:.4f} (frame by frame the two runs differ by {sum(per_frame) / len(per_frame):.5f} in the mean and "
+               f"{max(per_frame):.5f} at the most); coverage 0 on {covg[0]:.3f} of the pixels, partial on {covg[1]:.3f}, 1 on "
+               f"{covg[2]:.3f}; lowest: {min(err, key=err.get)} {err[min(err, key=err.get)]:.4f}", "",
+               "| setting | error (last frame's) | against plain | source 0 | 1 | 2 | 5 | 6 | clipped |", "|---|---|---|---|---|---|---|---|---|"]
+        for n in names:
+            base = err["plain, " + n.split(", ", 1)[1]] if ", " in n else err["plain"]
+            md.append(f"| {n} | {err[n]:.4f} ({rows[-1]['error'][n]:.4f}) | {100 * (err[n] / base - 1):+.1f} % | " +
+                      " | ".join(f"{src[n][v]:.3f}" for v in ("0", "1", "2", "5", "6")) + f" | {clip[n]:.2f} |")
+        md += ["", "| reprojected call | kernel ms (median, min-max) |", "|---|---|"]
+        for name, t in s["kernel_ms"].items():
+            md.append(f"| {name} | {t['median_ms']:.4f} ({t['min_ms']:.4f}-{t['max_ms']:.4f}) |")
+        md.append("")
+        scenes.append(dict(scene=s["scene"], repeat=round(repeat, 6), per_frame_spread_mean=round(sum(per_frame) / len(per_frame), 6),
+                           per_frame_spread_max=round(max(per_frame), 6), coverage=[round(v, 4) for v in covg],
+                           kernel_ms={n: [round(t[k], 5) for k in ("median_ms", "min_ms", "max_ms")]
+                                      for n, t in s["kernel_ms"].items()},
+                           mean_last_clipped={n: [round(err[n], 5), round(rows[-1]["error"][n], 5), round(clip[n], 3)] for n in names},
+                           source={n: [round(src[n][v], 4) for v in ("0", "1", "2", "5", "6")] for n in names},
+                           per_frame=dict({n: [round(r["error"][n], 5) for r in rows] for n in names},
+                                          raw=[round(r["raw"], 5) for r in rows], repeat=[round(r["repeat"], 5) for r in rows])))
+    small = dict({k: v for k, v in res.items() if k != "scenes"}, tail=[tail[0], tail[-1]], scenes=scenes)
+    text = re.sub(r"\[[^\[\]{}]*\]", lambda m: re.sub(r"\s+", " ", m.group(0)), json.dumps(small, indent=1))   # a list a line
+    with open(os.path.join(out, "temporal_cover_probe.json"), "w") as fh:
+        fh.write(text + "\n")
+    with open(os.path.join(out, "temporal_cover_probe.md"), "w") as fh:
+        fh.write("\n".join(md))
+    print("\n".join(md))
+
+
+def cover_main(args):
+    res = dict(nx=NX, ny=NY, frames=args.frames, spp=args.spp, ref_spp=args.ref_spp, max_history=YARDSTICK,
+               sigma_coverage=args.sigma_coverage, cover_clamp=args.cover_clamp,
+               settings={k: rtnw.TEMPORAL_DEFAULTS[k] for k in ("cos_normal", "sigma_depth")},
+               scenes=[cover_scene(s, args) for s in args.scenes])
+    cover_report(res, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default="temporal_probe_out")
@@ -244,7 +386,13 @@ def main():
     ap.add_argument("--clamp", action="store_true", help="measure rt_temporal_clamped instead (see above)")
     ap.add_argument("--radius", type=int, nargs="+", default=[1, 2, 3])
     ap.add_argument("--gamma", type=float, nargs="+", default=[0.5, 1.0, 1.5, 2.0, 3.0])
+    ap.add_argument("--cover", action="store_true", help="measure rt_temporal_cover instead (see above)")
+    ap.add_argument("--sigma-coverage", type=float, nargs="+", default=[0.125, 0.25, 0.5, 1.0])
+    ap.add_argument("--cover-clamp", type=float, nargs=2, default=[1, 0.5], metavar=("RADIUS", "GAMMA"))
     args = ap.parse_args()
+    args.cover_clamp = (int(args.cover_clamp[0]), float(args.cover_clamp[1]))
+    if args.cover:
+        return cover_main(args)
     if args.clamp:
         return clamp_main(args)
     os.makedirs(args.out, exist_ok=True)
