@@ -174,6 +174,14 @@ def lib():
         L.oracle_first_hits_desc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(OracleParams)] + \
             [ctypes.c_void_p] * 4
         L.oracle_first_hits_desc.restype = ctypes.c_int
+        L.oracle_trace_rays_desc.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + \
+            [ctypes.c_void_p] * 5
+        L.oracle_trace_rays.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 5
+        L.oracle_radiance_rays_desc.argtypes = [ctypes.c_void_p, ctypes.POINTER(OracleParams), ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.c_void_p]
+        L.oracle_radiance_rays.argtypes = [ctypes.POINTER(OracleParams), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        for f in (L.oracle_trace_rays_desc, L.oracle_trace_rays, L.oracle_radiance_rays_desc, L.oracle_radiance_rays):
+            f.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -292,6 +300,88 @@ def first_hits_desc(desc, cam, spec: RenderSpec):
     return dict(prim=prim, hit=prim >= 0, depth=depth, normal=normal, albedo=albedo)
 
 
+# rt_ray, rt_path_ray and rt_radiance as numpy records (include/rt_hip.h; the layouts of rtnw's)
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("dir", np.float32, 3), ("t_max", np.float32),
+                      ("time", np.float32), ("pad", np.float32, 3)])
+PATH_RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("time", np.float32), ("dir", np.float32, 3), ("skip", np.uint32),
+                           ("pixel", np.uint32), ("sample", np.uint32), ("pad", np.uint32, 2)])
+RADIANCE_DTYPE = np.dtype([("rgb", np.float32, 3), ("status", np.int32)])
+
+
+def _records(rays, dtype):
+    r = np.ascontiguousarray(rays)
+    if r.dtype != dtype:
+        raise TypeError(f"rays must be records of {dtype.names}")
+    return r.reshape(-1)
+
+
+def _trace(call, r, threads, materials):
+    n = len(r)
+    prim, t, depth = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    normal, albedo = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    rc = call(r.ctypes.data, n, threads, prim.ctypes.data, t.ctypes.data, depth.ctypes.data, normal.ctypes.data,
+              albedo.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle trace_rays failed: {rc}")
+    material = np.full(n, -1, np.int32) if materials is None else np.append(materials, -1).astype(np.int32)[prim]
+    return dict(prim=prim, material=material, t=t, depth=depth, normal=normal, albedo=albedo, pad=np.zeros((n, 2), np.int32))
+
+
+def trace_rays_desc(desc, rays, threads: int = 1):
+    """oracle_trace_rays_desc: the closest surface hit of each rt_ray record (rtnw.pack_rays) in
+    an rtnw.SceneDesc, media skipped, as the dict rtnw.Scene.trace_rays returns: prim (-1: miss),
+    material (the descriptor's, -1 on a miss) [n] int32, t, depth [n], normal, albedo [n, 3]
+    float32, pad [n, 2] zeros.  Valid rays only: no validity rule is restated."""
+    c = desc.contents
+    mats = np.array([c.prims[i].material for i in range(c.nprims)], np.int32)
+    dp = ctypes.cast(desc.ptr, ctypes.c_void_p)
+    return _trace(lambda *a: lib().oracle_trace_rays_desc(dp, *a), _records(rays, RAY_DTYPE), threads, mats)
+
+
+def trace_rays(scene: str, rays, threads: int = 1):
+    """oracle_trace_rays: the same over a built-in scene; prim is the leaf's place in list order
+    (depth first, media left out) and material is -1 throughout."""
+    if scene == "earth":
+        load_earth_image()
+    return _trace(lambda *a: lib().oracle_trace_rays(SCENES[scene], *a), _records(rays, RAY_DTYPE), threads, None)
+
+
+def _ray_params(scene, max_depth, background, seed, tmin, forward, media_after, threads):
+    return OracleParams(scene=scene, nx=1, ny=1, ns=1, max_depth=max_depth, background=1 if background == "sky" else 0,
+                        tmin=tmin, camera=0, rng=1, media_after=int(media_after), forward=int(forward), threads=threads,
+                        seed=seed)
+
+
+def _radiance(call, r):
+    out = np.zeros(len(r), RADIANCE_DTYPE)
+    rgb = np.zeros((len(r), 3), np.float32)
+    rc = call(r.ctypes.data, len(r), rgb.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle radiance_rays failed: {rc}")
+    out["rgb"] = rgb
+    return out
+
+
+def radiance_rays_desc(desc, rays, *, max_depth: int, background: str, seed: int = 0, tmin: float = 0.001,
+                       forward: bool = True, media_after: bool = True, threads: int = 1):
+    """oracle_radiance_rays_desc: 0 + de_nan(color()) of each rt_path_ray record
+    (rtnw.pack_path_rays) in an rtnw.SceneDesc as [n] records like rtnw.Scene.radiance_rays'
+    (rgb [n, 3] float32, status 0): the kernel's statement by default, the reference's order with
+    forward=False, media_after=False.  Valid rays only."""
+    p = _ray_params(-1, max_depth, background, seed, tmin, forward, media_after, threads)
+    dp = ctypes.cast(desc.ptr, ctypes.c_void_p)
+    return _radiance(lambda *a: lib().oracle_radiance_rays_desc(dp, ctypes.byref(p), *a), _records(rays, PATH_RAY_DTYPE))
+
+
+def radiance_rays(scene: str, rays, *, max_depth: int, background: str, seed: int = 0, tmin: float = 0.001,
+                  forward: bool = True, media_after: bool = True, threads: int = 1):
+    """oracle_radiance_rays: the same over a built-in scene."""
+    if scene == "earth":
+        load_earth_image()
+    p = _ray_params(SCENES[scene], max_depth, background, seed, tmin, forward, media_after, threads)
+    return _radiance(lambda *a: lib().oracle_radiance_rays(ctypes.byref(p), *a), _records(rays, PATH_RAY_DTYPE))
+
+
 def feature_means(fh):
     """What rt_render_features writes for those samples: each buffer's samples added in sample
     order in float32, the sum times float(1.0 / spp).  albedo, normal [h, w, 3]; depth,
@@ -390,6 +480,55 @@ def ref_render(spec: RenderSpec, workdir: str, rows: tuple | None = None, timing
         import json
         tinfo = json.loads(res.stdout.strip().splitlines()[-1])
     return mean, text, tinfo
+
+
+_ref_rays = None
+
+
+def have_ref_rays() -> bool:
+    """Whether the reference binary is there and has the ray mode (ref_harness.cpp --rays,
+    --path-rays).  oracle/_ref is not in git: where the reference tree is absent `make -C oracle`
+    rebuilds nothing and a binary kept from an earlier build, which may predate the mode, is what
+    runs.  Asked of the binary by having it do the job on no records: a binary with the mode
+    reads an empty file, writes an empty one and exits 0; one without it ends in usage() (2)."""
+    global _ref_rays
+    if _ref_rays is None:
+        _ref_rays = False
+        if have_ref():
+            try:
+                res = subprocess.run([REF_BIN, "--scene", "edge_single", "--rays", os.devnull, "--hits", os.devnull,
+                                      "--path-rays", os.devnull, "--radiance", os.devnull], capture_output=True, timeout=60)
+                _ref_rays = res.returncode == 0
+            except (OSError, subprocess.TimeoutExpired):
+                pass
+    return _ref_rays
+
+
+REF_HIT_FIELDS = 9   # the harness's answer per ray: hit (0 or 1), t, depth, normal[3], albedo[3]
+
+
+def ref_trace_rays(scene: str, rays, workdir: str) -> np.ndarray:
+    """The compiled reference's own world->hit on each rt_ray record: [n, 9] float32 of hit, t,
+    depth, normal, albedo (a miss: zeros and an albedo of 1, as the oracle reports it)."""
+    r = _records(rays, RAY_DTYPE)
+    src, dst = os.path.join(workdir, "rays.bin"), os.path.join(workdir, "hits.f32")
+    r.tofile(src)
+    subprocess.run([REF_BIN, "--scene", scene, "--rays", src, "--hits", dst, "--assets", os.path.dirname(EARTH_PNG)],
+                   capture_output=True, check=True)
+    return np.fromfile(dst, dtype=np.float32).reshape(len(r), REF_HIT_FIELDS)
+
+
+def ref_radiance_rays(scene: str, rays, workdir: str, *, max_depth: int, background: str, seed: int = 0,
+                      tmin: float = 0.001) -> np.ndarray:
+    """The compiled reference's own color() on each rt_path_ray record, the counter stream
+    restarted at the record's key and advanced by its skip: [n, 3] float32."""
+    r = _records(rays, PATH_RAY_DTYPE)
+    src, dst = os.path.join(workdir, "path_rays.bin"), os.path.join(workdir, "radiance.f32")
+    r.tofile(src)
+    subprocess.run([REF_BIN, "--scene", scene, "--path-rays", src, "--radiance", dst, "--seed", str(seed),
+                    "--depth", str(max_depth), "--bg", background, "--tmin", repr(tmin),
+                    "--assets", os.path.dirname(EARTH_PNG)], capture_output=True, check=True)
+    return np.fromfile(dst, dtype=np.float32).reshape(len(r), 3)
 
 
 def ref_dump(scene: str, workdir: str) -> str:

@@ -19,6 +19,9 @@
 //     see DESIGN.md §RNG), and constant_medium draws come from a (sample, bounce,
 //     medium) keyed stream — selected by wrapping each medium in `medium_tag`.
 //
+//   * Ray mode (--rays / --path-rays, below): the reference's own world->hit and color()
+//     on records a caller supplies, for the oracle's entries on free rays.
+//
 // Nothing from the reference is copied into the repository; outputs go to
 // oracle/_ref/ (git-ignored).  Build recipe: oracle/Makefile.
 
@@ -338,12 +341,89 @@ static hitable *edge_chains() {   // instance chains, nested checkers, specular 
     return new hitable_list(l, i);
 }
 
+// ------------------------------------------------------------------ ray mode
+// Caller-supplied rays (include/rt_hip.h rt_ray, rt_path_ray: 48-byte records read raw), answered
+// by the reference's own code: --rays IN --hits OUT runs world->hit(ray(o, d, time), t_min,
+// min(t_max, MAXFLOAT), rec) and writes 9 floats per ray (hit 0 / 1, t, depth = t * |d|, normal,
+// the hit material's colour; a miss: zeros and a colour of 1); --path-rays IN --radiance OUT
+// restarts the counter stream at the record's key, advances it by `skip` draws and writes
+// 0 + de_nan(color(r, world, 0)), three floats, with --seed, --depth, --bg and --tmin as the
+// pixel loop uses them.  The records mirror rt_hip.h's layout; nothing of it is included here.
+struct ray_record { float origin[3], t_min, dir[3], t_max, time, pad[3]; };
+struct path_ray_record { float origin[3], time, dir[3]; uint32_t skip, pixel, sample, pad[2]; };
+static_assert(sizeof(ray_record) == 48 && sizeof(path_ray_record) == 48, "rt_ray and rt_path_ray are 48 bytes");
+
+template <class T> static bool read_records(const std::string &path, std::vector<T> &v) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    fseek(f, 0, SEEK_END);
+    long bytes = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    v.resize((size_t)bytes / sizeof(T));
+    bool ok = fread(v.data(), sizeof(T), v.size(), f) == v.size();
+    fclose(f);
+    return ok;
+}
+static bool write_floats(const std::string &path, const std::vector<float> &v) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    bool ok = fwrite(v.data(), sizeof(float), v.size(), f) == v.size();
+    return fclose(f) == 0 && ok;
+}
+static vec3 hit_colour(const hit_record &rec) {   // the colour rt_render_features records for a hit
+    if (auto *l = dynamic_cast<const lambertian *>(rec.mat_ptr)) return l->albedo->value(rec.u, rec.v, rec.p);
+    if (auto *m = dynamic_cast<const metal *>(rec.mat_ptr)) return m->albedo;
+    if (auto *e = dynamic_cast<const diffuse_light *>(rec.mat_ptr)) return e->emit->value(rec.u, rec.v, rec.p);
+    if (auto *i = dynamic_cast<const isotropic *>(rec.mat_ptr)) return i->albedo->value(rec.u, rec.v, rec.p);
+    return vec3(1, 1, 1);                         // dielectric
+}
+static int ray_mode(hitable *world, const std::string &rays_in, const std::string &hits_out, const std::string &path_rays_in,
+                    const std::string &radiance_out, uint64_t seed) {
+    if (!rays_in.empty()) {
+        std::vector<ray_record> rays;
+        if (hits_out.empty() || !read_records(rays_in, rays)) return 2;
+        std::vector<float> out(rays.size() * 9, 0.0f);
+        for (size_t q = 0; q < rays.size(); q++) {
+            const ray_record &y = rays[q];
+            ray r(vec3(y.origin[0], y.origin[1], y.origin[2]), vec3(y.dir[0], y.dir[1], y.dir[2]), y.time);
+            hit_record rec;
+            memset((void *)&rec, 0, sizeof rec);   // u, v of a primitive that sets none (moving_sphere) read as 0
+            float *o = &out[q * 9];
+            if (world->hit(r, y.t_min, y.t_max < MAXFLOAT ? y.t_max : MAXFLOAT, rec)) {
+                vec3 a = hit_colour(rec);
+                o[0] = 1; o[1] = rec.t; o[2] = rec.t * r.direction().length();
+                for (int k = 0; k < 3; k++) { o[3 + k] = rec.normal[k]; o[6 + k] = a[k]; }
+            } else o[6] = o[7] = o[8] = 1.0f;
+        }
+        if (!write_floats(hits_out, out)) return 2;
+    }
+    if (!path_rays_in.empty()) {
+        std::vector<path_ray_record> rays;
+        if (radiance_out.empty() || g_mode != 1 || !read_records(path_rays_in, rays)) return 2;
+        bool use_reference_color = (g_bg == 0 && g_max_depth == 50 && g_tmin == 0.001f);
+        std::vector<float> out(rays.size() * 3);
+        for (size_t q = 0; q < rays.size(); q++) {
+            const path_ray_record &y = rays[q];
+            g_key = sample_key(seed, y.pixel, y.sample); g_x = g_key & 0xFFFFFFFFFFFFull; g_bounce = 0;
+            for (uint32_t k = 0; k < y.skip; k++) (void)drand48();
+            ray r(vec3(y.origin[0], y.origin[1], y.origin[2]), vec3(y.dir[0], y.dir[1], y.dir[2]), y.time);
+            vec3 col(0, 0, 0);
+            vec3 temp = use_reference_color ? color(r, world, 0) : color_ex(r, world, 0);
+            col += de_nan(temp);                  // main.cpp:311-312 with one sample
+            for (int k = 0; k < 3; k++) out[q * 3 + k] = col[k];
+        }
+        if (!write_floats(radiance_out, out)) return 2;
+    }
+    return 0;
+}
+
 // ----------------------------------------------------------------------- CLI
 static void usage() {
     fprintf(stderr,
         "ref_render --scene NAME [--nx N --ny N --ns N --depth D --bg black|sky --tmin T]\n"
         "           [--cam cornell|random|final_alt] [--rng canonical|counter --seed S]\n"
         "           [--rows J0:J1] [--ppm FILE] [--fb FILE] [--dump FILE] [--perlin FILE] [--time] [--accel flat|bvh]\n"
+        "           [--rays IN --hits OUT] [--path-rays IN --radiance OUT]   (raw rt_ray / rt_path_ray records)\n"
         "  scenes: random_scene random_motion cornell_box cornell_smoke final simple_light two_spheres test\n"
         "          edge_empty edge_single edge_degenerate edge_chains (sky, random camera)\n");
     exit(2);
@@ -351,6 +431,7 @@ static void usage() {
 
 int main(int argc, char **argv) {
     std::string scene = "final", cam_name = "", bg = "", rng = "canonical", ppm, fb, dump, perlin_out, assets, accel = "flat";
+    std::string rays_in, hits_out, path_rays_in, radiance_out;
     int nx = 40, ny = 40, ns = 4, depth = -1, j_lo = 0, j_hi = -1; bool timing = false;
     double tmin = 0.001; uint64_t seed = 0;
     for (int a = 1; a < argc; a++) {
@@ -374,6 +455,10 @@ int main(int argc, char **argv) {
         else if (k == "--time") timing = true;
         else if (k == "--assets") assets = val();
         else if (k == "--accel") accel = val();
+        else if (k == "--rays") rays_in = val();
+        else if (k == "--hits") hits_out = val();
+        else if (k == "--path-rays") path_rays_in = val();
+        else if (k == "--radiance") radiance_out = val();
         else usage();
     }
     if (j_hi < 0) j_hi = ny;
@@ -411,6 +496,8 @@ int main(int argc, char **argv) {
     else usage();
     std::cout.rdbuf(saved);
 
+    if (!path_rays_in.empty()) rng = "counter";   // a record names its stream by the counter key
+
     if (!dump.empty()) {
         g_dump = fopen(dump.c_str(), "w");
         dump_node(world, "");
@@ -446,6 +533,8 @@ int main(int argc, char **argv) {
         world = counted;
         g_mode = 1;
     } else if (rng != "canonical") usage();
+
+    if (!rays_in.empty() || !path_rays_in.empty()) return ray_mode(world, rays_in, hits_out, path_rays_in, radiance_out, seed);
 
     int rows = j_hi - j_lo;
     std::vector<float> out((size_t)rows * nx * 3);

@@ -1198,6 +1198,104 @@ int oracle_first_hits_desc(const rt_scene_desc *d, const rt_camera_desc *c, cons
     return 0;
 }
 
+/* ------------------------------------------------ caller-supplied rays
+ * The two searches over a built scene; the descriptor entries and their built-in-scene twins
+ * differ only in where the scene comes from. */
+static void trace_rays_scene(const scene_t *scp, const rt_ray *rays, int64_t n, int nt, int32_t *prim, float *t, float *depth,
+                             float *normal, float *albedo) {
+    const scene_t sc = *scp;
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
+    for (int64_t q = 0; q < n; q++) {
+        const rt_ray *y = &rays[q];
+        ray_t r = R(V(y->origin[0], y->origin[1], y->origin[2]), V(y->dir[0], y->dir[1], y->dir[2]), y->time);
+        rng_t g; memset(&g, 0, sizeof g); g.counter = 1;
+        hctx_t cx = { &g, 0, 1 };
+        hit_t rec; memset(&rec, 0, sizeof rec);
+        float tmax = y->t_max < RT_MAXFLOAT ? y->t_max : RT_MAXFLOAT;   /* +inf, or at or above FLT_MAX: MAXFLOAT */
+        if (obj_hit(sc.world, &r, y->t_min, tmax, &rec, &cx)) {
+            v3 a = mat_colour(&rec);
+            prim[q] = rec.prim;
+            t[q] = rec.t;
+            depth[q] = rec.t * vlen(r.B);
+            for (int k = 0; k < 3; k++) { normal[3 * q + k] = rec.normal.e[k]; albedo[3 * q + k] = a.e[k]; }
+        } else {
+            prim[q] = -1;
+            t[q] = 0;
+            depth[q] = 0;
+            for (int k = 0; k < 3; k++) { normal[3 * q + k] = 0; albedo[3 * q + k] = 1.0f; }
+        }
+    }
+}
+
+static void radiance_rays_scene(const scene_t *scp, const oracle_params *p, const rt_path_ray *rays, int64_t n, float *rgb) {
+    const scene_t sc = *scp;
+    int nt = p->threads > 0 ? p->threads : 1;
+#pragma omp parallel for schedule(dynamic, 16) num_threads(nt)
+    for (int64_t q = 0; q < n; q++) {
+        const rt_path_ray *y = &rays[q];
+        rng_t g; memset(&g, 0, sizeof g); g.counter = 1;
+        run_t rn = { &sc, p, 0, 0 };
+        rng_seed_sample(&g, sample_key(p->seed, y->pixel, y->sample));
+        g.nmedia = sc.nmedia;
+        for (uint32_t k = 0; k < y->skip; k++) (void)rng_next(&g);      /* the draws the caller spent */
+        ray_t r = R(V(y->origin[0], y->origin[1], y->origin[2]), V(y->dir[0], y->dir[1], y->dir[2]), y->time);
+        v3 c = de_nan(p->forward ? color_forward(&rn, r, &g) : color_right(&rn, &r, 0, &g));
+        c = vadd(V(0, 0, 0), c);                                        /* the one-sample sum: -0 becomes +0 */
+        for (int k = 0; k < 3; k++) rgb[3 * q + k] = c.e[k];
+    }
+}
+
+int oracle_trace_rays_desc(const rt_scene_desc *d, const rt_ray *rays, int64_t n, int threads, int32_t *prim, float *t,
+                           float *depth, float *normal, float *albedo) {
+    if (!d || n < 0 || (n > 0 && (!rays || !prim || !t || !depth || !normal || !albedo))) return -1;
+    scene_t sc;
+    if (scene_from_desc(&sc, d) != 0) { scene_free(&sc); return -2; }
+    trace_rays_scene(&sc, rays, n, threads > 0 ? threads : 1, prim, t, depth, normal, albedo);
+    scene_free(&sc);
+    return 0;
+}
+
+int oracle_radiance_rays_desc(const rt_scene_desc *d, const oracle_params *p, const rt_path_ray *rays, int64_t n, float *rgb) {
+    if (!d || !p || n < 0 || (n > 0 && (!rays || !rgb))) return -1;
+    scene_t sc;
+    if (scene_from_desc(&sc, d) != 0) { scene_free(&sc); return -2; }
+    radiance_rays_scene(&sc, p, rays, n, rgb);
+    scene_free(&sc);
+    return 0;
+}
+
+/* A built-in scene's leaves numbered in list order, depth first (the order of oracle_scene_dump's
+ * lines outside the media): what the built-in twins report as `prim`. */
+static void number_leaves(obj_t *o, int *next) {
+    switch (o->kind) {
+    case OB_LIST: for (int i = 0; i < o->nkids; i++) number_leaves(o->kids[i], next); break;
+    case OB_BOX: case OB_FLIP: case OB_TRANSLATE: case OB_ROTY: number_leaves(o->child, next); break;
+    case OB_MEDIUM: break;
+    default: o->id = (*next)++; break;
+    }
+}
+
+int oracle_trace_rays(int scene, const rt_ray *rays, int64_t n, int threads, int32_t *prim, float *t, float *depth,
+                      float *normal, float *albedo) {
+    if (n < 0 || (n > 0 && (!rays || !prim || !t || !depth || !normal || !albedo))) return -1;
+    scene_t sc;
+    if (scene_build(&sc, scene, NULL) != 0) return -2;
+    int next = 0;
+    number_leaves(sc.world, &next);
+    trace_rays_scene(&sc, rays, n, threads > 0 ? threads : 1, prim, t, depth, normal, albedo);
+    scene_free(&sc);
+    return 0;
+}
+
+int oracle_radiance_rays(const oracle_params *p, const rt_path_ray *rays, int64_t n, float *rgb) {
+    if (!p || n < 0 || (n > 0 && (!rays || !rgb))) return -1;
+    scene_t sc;
+    if (scene_build(&sc, p->scene, NULL) != 0) return -2;
+    radiance_rays_scene(&sc, p, rays, n, rgb);
+    scene_free(&sc);
+    return 0;
+}
+
 void oracle_quantize(const float *mean, int n, uint8_t *rgb) {          /* main.cpp:316-325 */
     for (int q = 0; q < n; q++) {
         for (int k = 0; k < 3; k++) {

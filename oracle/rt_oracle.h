@@ -96,6 +96,30 @@ int oracle_render_desc(const rt_scene_desc *d, const rt_camera_desc *cam, const 
 int oracle_first_hits_desc(const rt_scene_desc *d, const rt_camera_desc *cam, const oracle_params *p, int32_t *prim,
                            float *depth, float *normal, float *albedo);
 
+/* Caller-supplied rays (what rt_trace_rays and rt_radiance_rays answer, rt_hip.h): no camera.
+ *
+ * oracle_trace_rays_desc: for each rt_ray, hitable_list::hit(ray(origin, dir, time), t_min,
+ * min(t_max, MAXFLOAT), rec) on the tree oracle_render_desc builds, media skipped.  prim, depth,
+ * normal and albedo as oracle_first_hits_desc reports them, and t the hit record's (0 on a miss);
+ * arrays of n (x 3).  No validity rule is restated: the callers send valid rays only.
+ *
+ * oracle_radiance_rays_desc: for each rt_path_ray the sample stream is restarted at
+ * sample_key(p->seed, pixel, sample) and advanced by `skip` draws, the medium stream starts at
+ * its usual key with segment 0, and rgb[3] = 0 + de_nan(color(ray, world, 0)) with p's tmin,
+ * max_depth, background, media_after and forward (the one-sample sum of a render: -0 comes back
+ * +0).  Of p only those, seed and threads are read.
+ *
+ * oracle_trace_rays / oracle_radiance_rays: the same over a built-in scene (`scene`, p->scene),
+ * which is what pins both to the reference (tests/golden rays_*).  Their prim is the leaf's
+ * place in list order, depth first, media left out.
+ * All return 0, -1 for a null argument, -2 for a scene that cannot be built. */
+int oracle_trace_rays_desc(const rt_scene_desc *d, const rt_ray *rays, int64_t n, int threads, int32_t *prim, float *t,
+                           float *depth, float *normal, float *albedo);
+int oracle_radiance_rays_desc(const rt_scene_desc *d, const oracle_params *p, const rt_path_ray *rays, int64_t n, float *rgb);
+int oracle_trace_rays(int scene, const rt_ray *rays, int64_t n, int threads, int32_t *prim, float *t, float *depth,
+                      float *normal, float *albedo);
+int oracle_radiance_rays(const oracle_params *p, const rt_path_ray *rays, int64_t n, float *rgb);
+
 /* Quantises a mean-radiance buffer exactly like main.cpp:315-328 into RGB bytes. */
 void oracle_quantize(const float *mean, int n_pixels, uint8_t *rgb);
 

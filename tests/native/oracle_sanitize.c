@@ -4,7 +4,8 @@
  * clipped output rectangle, the quantiser, the PPM writer and the RNG helpers; and the
  * descriptor entry points (oracle_render_desc, oracle_first_hits_desc) on a hand-made
  * descriptor with every primitive, texture and material kind, a 6-op chain and 70 media;
- * and all three render entry points at the ABI's limits (limits_check).
+ * all three render entry points at the ABI's limits (limits_check); and the entries for
+ * caller-supplied rays with their built-in twins (rays_check).
  * Exit 0 = every render returned 0 and no sanitizer fired. */
 #include <stdio.h>
 #include <stdlib.h>
@@ -140,9 +141,56 @@ static int limits_check(void) {
     return bad;
 }
 
+/* The entries for caller-supplied rays on a small batch: rays from inside and outside desc_check's
+ * descriptor with both signs of t_min, a finite and an infinite t_max and the ends of the shutter;
+ * records with skip 0 and 192 and the ends of the pixel and sample range, in both fold orders
+ * and both media orders; the same through the built-in twins; and n = 0 with null arrays. */
+static int rays_check(void) {
+    enum { N = 24 };
+    static rt_ray rays[N];
+    static rt_path_ray paths[N];
+    static int32_t prim[N];
+    static float t[N], depth[N], nrm[N * 3], alb[N * 3], rgb[N * 3];
+    int bad = 0, hits = 0;
+    for (int i = 0; i < N; i++) {
+        const float o[3] = {-2.0f + 0.35f * (float)(i % 12), 0.4f + 0.1f * (float)(i % 5), i < 12 ? 6.0f : 0.9f};
+        const float d[3] = {0.11f * (float)(i % 7) - 0.3f, 0.07f - 0.05f * (float)(i % 3), i % 4 == 3 ? 0.8f : -1.0f};
+        memset(&rays[i], 0, sizeof rays[i]);
+        memset(&paths[i], 0, sizeof paths[i]);
+        for (int k = 0; k < 3; k++) { rays[i].origin[k] = paths[i].origin[k] = o[k]; rays[i].dir[k] = paths[i].dir[k] = d[k]; }
+        rays[i].t_min = i % 3 == 2 ? -0.5f : (i % 3 ? 0.0f : 0.001f);
+        rays[i].t_max = i % 5 == 4 ? 3.0f : 1.0f / 0.0f;
+        rays[i].time = paths[i].time = i % 2 ? 1.0f : 0.0f;
+        paths[i].skip = i % 3 == 0 ? 0u : (i % 3 == 1 ? 192u : 5u);
+        paths[i].pixel = i % 4 == 0 ? 0u : (i % 4 == 1 ? 0xFFFFFFFFu : 77u * (uint32_t)i);
+        paths[i].sample = i % 5 == 0 ? 0xFFFFFFFFu : (uint32_t)i;
+    }
+    if (oracle_trace_rays_desc(&g_desc, rays, N, 2, prim, t, depth, nrm, alb) != 0) { printf("rays: descriptor trace failed\n"); bad++; }
+    for (int i = 0; i < N; i++) hits += prim[i] >= 0;
+    if (hits == 0 || hits == N) { printf("rays: %d of %d rays hit\n", hits, N); bad++; }
+    if (oracle_trace_rays(ORACLE_SCENE_EDGE_CHAINS, rays, N, 1, prim, t, depth, nrm, alb) != 0) { printf("rays: built-in trace failed\n"); bad++; }
+    for (int mode = 0; mode < 2; mode++) {
+        oracle_params p;
+        memset(&p, 0, sizeof p);
+        p.scene = ORACLE_SCENE_EDGE_CHAINS; p.max_depth = mode ? 50 : 1; p.background = mode; p.tmin = 0.001f; p.rng = 1;
+        p.media_after = mode; p.forward = mode; p.threads = 2; p.seed = mode ? ~(uint64_t)0 : 9;
+        if (oracle_radiance_rays_desc(&g_desc, &p, paths, N, rgb) != 0) { printf("rays: descriptor radiance %d failed\n", mode); bad++; }
+        if (oracle_radiance_rays(&p, paths, N, rgb) != 0) { printf("rays: built-in radiance %d failed\n", mode); bad++; }
+        for (int i = 0; i < 3 * N; i++) if (!(rgb[i] >= 0)) { printf("rays: mode %d: component %d is negative or NaN\n", mode, i); bad++; break; }
+        if (oracle_radiance_rays_desc(&g_desc, &p, NULL, 0, NULL) != 0 || oracle_radiance_rays_desc(&g_desc, &p, NULL, 1, rgb) != -1) {
+            printf("rays: radiance argument checks\n"); bad++;
+        }
+    }
+    if (oracle_trace_rays_desc(&g_desc, NULL, 0, 1, NULL, NULL, NULL, NULL, NULL) != 0 ||
+        oracle_trace_rays_desc(NULL, rays, N, 1, prim, t, depth, nrm, alb) != -1 ||
+        oracle_trace_rays(99, rays, N, 1, prim, t, depth, nrm, alb) != -2) { printf("rays: trace argument checks\n"); bad++; }
+    return bad;
+}
+
 int main(void) {
     int bad = desc_check();
     bad += limits_check();
+    bad += rays_check();
     static float img[24 * 16 * 3];
     static uint8_t rgb[24 * 16 * 3];
     static char text[24 * 16 * 16 + 64];
